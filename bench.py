@@ -1,6 +1,6 @@
 """Benchmark of the SoftGroup hot path on MI355X: ScanNet-v2-like inference (BASELINE config 2).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one full ``forward_test`` (voxel pooling -> sparse U-Net -> point heads -> soft
@@ -8,7 +8,11 @@ grouping -> proposal voxelisation -> tiny U-Net -> instance heads -> masks/RLE) 
 150k-point scene whose tensors are already resident in HBM.  Scenes shard one per GPU (no
 data-path collective): weak scaling, value = scans/s summed over ranks.
 
-Besides the headline line the JSON carries
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` (the arrays the last
+timed step returned, dump_outputs) and prints the headline line.  With ``--full`` the JSON also
+carries (``--no-roofline`` / ``--no-cpu-baseline`` / ``--no-legs`` leave parts out)
+  latency       ms_per_step_one_scan_at_a_time, ms_per_step_unpipelined / latency_ms and vs_baseline
+  ddp           (N > 1) the gradient all-reduce and a short DDP training leg (ddp_leg)
   roofline      the dominant kernel (sparse-conv gather implicit GEMM): algorithmic gather/scatter
                 bytes (SURVEY 8d B_gs) / HIP-event kernel time vs the 8 TB/s HBM roof, and its
                 fp32 MFMA rate vs 157.3 TFLOP/s
@@ -63,9 +67,15 @@ def parse():
                          'profiles/r06_token_matrix.txt, end of round 6)')
     ap.add_argument('--switch-interval-us', type=int, default=0,
                     help='sys.setswitchinterval for the process (0 = leave CPython\'s 5 ms)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-legs', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also measure everything else: latency, stages, roofline, CPU baseline '
+                         'and parity, the config / measurement legs, and with N > 1 the DDP leg (off: the plain run '
+                         'sets up, warms up, times the steps, writes --dump-outputs and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path returned for its last step as DIR/<name>.npy (rank 0)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(with --full) skip the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='(with --full) skip the roofline')
+    ap.add_argument('--no-legs', action='store_true', help='(with --full) skip the legs')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help="'gloo' + --stub: the launch / sharding / timing plumbing on CPU (tests)")
     ap.add_argument('--stub', action='store_true',
@@ -126,7 +136,7 @@ def finish_n_gt_1(out, args, rank, world, local_rank, stub):
 
     threading.Thread(target=watchdog, daemon=True).start()
     try:
-        ddp = ddp_leg(args, rank, world, local_rank, stub)
+        ddp = ddp_leg(args, rank, world, local_rank, stub) if args.full else 'not run (--full)'
         cores = [None] * world
         dist.all_gather_object(cores, args._core_slice)
         out['ddp'] = ddp
@@ -791,6 +801,48 @@ def reference_cpu_ops_leg(model, batch):
     return rec
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MASK_SAMPLE = 16384      # points of the fixed, seeded sample the instance masks are written at
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what the caller of the timed path received for the last timed step, as
+    path/<name>.npy.  Every numeric array of the result dict is written whole (float32 where that is
+    exact for its dtype, float64 otherwise); the instances as label / confidence / mask point count
+    per instance and their masks decoded at a fixed sample of points (seed 0, the same for every run
+    with the same --points).  At most DUMP_BUDGET_BYTES in all."""
+    import numpy as np
+    from softgroup_amd.util.rle import rle_decode
+    exact32 = (np.bool_, np.int8, np.uint8, np.int16, np.uint16, np.float16, np.float32)
+    arrays = {}
+    for k in sorted(res.keys()):
+        v = res[k]
+        if isinstance(v, torch.Tensor):
+            v = v.cpu().numpy()
+        if isinstance(v, np.ndarray) and v.dtype.kind in 'biuf':
+            arrays[k] = v.astype(np.float32 if v.dtype.type in exact32 else np.float64)
+    insts = res.get('pred_instances')
+    if insts is not None:
+        arrays['pred_instances_label_id'] = np.array([float(p['label_id']) for p in insts], np.float64)
+        arrays['pred_instances_conf'] = np.array([float(p['conf']) for p in insts], np.float64)
+        masks = [rle_decode(p['pred_mask']) if isinstance(p['pred_mask'], dict) else np.asarray(p['pred_mask'])
+                 for p in insts]
+        arrays['pred_instances_mask_points'] = np.array([float(m.sum()) for m in masks], np.float64)
+        n_pts = len(masks[0]) if masks else 0
+        used = sum(a.nbytes for a in arrays.values())
+        n_sample = min(n_pts, DUMP_MASK_SAMPLE, (DUMP_BUDGET_BYTES - used - 8 * DUMP_MASK_SAMPLE) // max(4 * len(masks), 1))
+        idx = np.sort(np.random.default_rng(0).choice(n_pts, n_sample, replace=False)) if n_pts else np.zeros(0, np.int64)
+        arrays['pred_instances_mask_sample_index'] = idx.astype(np.float64)
+        arrays['pred_instances_mask_sample'] = (np.stack([m[idx] for m in masks]) if masks
+                                                else np.zeros((0, n_sample))).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, f'--dump-outputs: {total} bytes over the {DUMP_BUDGET_BYTES} budget'
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+    return sorted(arrays)
+
+
 def timed_steps(step, resolve, steps, sync_all):
     """the contract's timed region: EXACTLY `steps` steps between two barrier+synchronize brackets.
     Also returns the ms/step of each third of the region (host time stamps taken as results of
@@ -983,6 +1035,7 @@ def main():
             gc.freeze()
         issued = iter(range(args.steps))
         checked = iter(range(args.steps))
+        last = []           # --dump-outputs: the result of the last timed step, kept past the region
 
         def step():
             return model(batches[next(issued) % n_scenes])
@@ -991,9 +1044,12 @@ def main():
             # (inside the timed region) the result is fully materialised and compared with the scene's
             # one-at-a-time digest: a scan in flight next to others must return the same bits
             r.resolve()
+            i = next(checked)
+            if args.dump_outputs and i == args.steps - 1:
+                last.append(r)
             if os.environ.get('SG_BENCH_SKIP_DIGEST'):      # developer diagnosis only: what the check costs
-                return next(checked) >= 0
-            return (r['result_digest'] if digest_on_worker else result_digest(r)) == alone[next(checked) % n_scenes]
+                return i >= 0
+            return (r['result_digest'] if digest_on_worker else result_digest(r)) == alone[i % n_scenes]
 
         elapsed, rets, windows = timed_steps(step, consume, args.steps, sync_all)
     model.scan_result_hook = None
@@ -1011,7 +1067,7 @@ def main():
         'metric': 'scans/sec ScanNet-v2-like inference (softgroup_scannet.yaml, full forward_test)',
         'value': round(value, 3), 'unit': 'scans/s', 'n_gpus': world, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3), 'higher_is_better': True,
-        'scaling': 'weak', 'vs_baseline': None,      # filled below from the single-scan latency
+        'scaling': 'weak', 'vs_baseline': None,      # filled below from the single-scan latency (--full)
         'vs_baseline_throughput': round(value / world / (1000.0 / REF_MS_PER_SCAN), 3),
         'dtype': 'f32', 'data': 'synthetic',
         'config': {
@@ -1041,7 +1097,12 @@ def main():
     }
     model.scan_contexts = 1
 
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0])
+    del last
+
+    # everything below the headline runs with --full only
+    if rank == 0 and args.full:
         # one scan at a time: (a) with the result formatting of scan i overlapping scan i+1 on the
         # results thread, (b) with everything in line -- the latency of a single scan
         with torch.no_grad():
@@ -1081,12 +1142,12 @@ def main():
         _lib.lib().sg_device_info(name, 128, _lib.C.byref(cu), _lib.C.byref(clk))
         out['device'] = {'name': name.value.decode(), 'cus': cu.value, 'clock_khz': clk.value}
 
-    if rank == 0 and world == 1 and not args.no_legs:
+    if rank == 0 and world == 1 and args.full and not args.no_legs:
         # before anything touches the CPU oracle: its OpenMP team keeps spinning on the host cores
         # for a while and slows every host-side step of these legs (octree build, numpy) many-fold
         out['legs'] = config_legs(args)
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # dominant kernel: gather_conv_persistent_kernel (sparse-conv implicit GEMM)
         # (a) algorithmic bytes / flops per launch: one forward on the module path, which makes one
         #     Python call per conv launch (same kernels as the native executor of the timed region);
@@ -1189,7 +1250,7 @@ def main():
             'hbm': hbm,
         }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import oracle  # checker only: CPU restatement of the reference model
         from oracle import parity
         oracle.build()
@@ -1221,7 +1282,7 @@ def main():
             'reference_ops': ref_ops,
         }
 
-    if rank == 0 and world == 1 and not args.no_legs:
+    if rank == 0 and world == 1 and args.full and not args.no_legs:
         out.setdefault('legs', {}).update(measurement_legs(args, model, batch, xyz, rgb, inst))
 
     if dist_on:

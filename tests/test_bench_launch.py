@@ -92,7 +92,7 @@ def test_n_gt_1_line_carries_the_ddp_leg_and_the_rank_core_slices():
     and the slice of host cores every rank bound itself to (disjoint slices; pinned result staging of
     a rank bounded by 12 MB x scan threads x 2)."""
     out = _run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '4', '--warmup', '1', '--backend', 'gloo',
-                '--stub'])
+                '--stub', '--full'])
     d = out['ddp']
     assert d['allreduce_bytes'] == 2919208 and d['backend'] == 'gloo'
     assert 0 < d['allreduce_ms_min'] <= d['allreduce_ms_median']
@@ -114,8 +114,53 @@ def test_n_gt_1_line_survives_a_rank_that_never_joins_the_ddp_leg():
     import time
     t0 = time.time()
     out = _run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '4', '--warmup', '1', '--backend', 'gloo',
-                '--stub', '--stub-ddp-hang-rank', '1'], env={'SG_BENCH_DDP_DEADLINE_S': '8'})
+                '--stub', '--full', '--stub-ddp-hang-rank', '1'], env={'SG_BENCH_DDP_DEADLINE_S': '8'})
     assert time.time() - t0 < 120
     assert out['n_gpus'] == 2 and out['ranks_seen'] == 2 and out['value'] > 0
     assert 'did not finish within 8 s' in out['ddp']['error']
     assert out['legs'] == 'skipped (N>1)'
+
+
+def test_plain_n_gt_1_run_leaves_the_ddp_leg_to_full():
+    """without --full the N > 1 job prints the headline and runs no DDP leg"""
+    out = _run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '4', '--warmup', '1', '--backend', 'gloo',
+                '--stub'])
+    assert out['n_gpus'] == 2 and out['steps'] == 4 and out['ms_per_step'] >= 2.0
+    assert out['ddp'] == 'not run (--full)'
+
+
+def test_dump_outputs_writes_every_array_of_the_result(tmp_path):
+    """--dump-outputs: the dense arrays whole in float32 / float64 with their values, the instances as
+    label / confidence / point count and their masks at a seeded point sample; the same files twice"""
+    import importlib.util
+    import numpy as np
+    from softgroup_amd.util.rle import rle_decode, rle_encode
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    n = 50000
+    masks = [(rng.random(n) < p).astype(np.uint8) for p in (0.01, 0.2, 0.5)]
+    res = dict(coords_float=rng.random((n, 3), dtype=np.float32), semantic_preds=rng.integers(0, 20, n),
+               offset_preds=rng.random((n, 3), dtype=np.float32), scan_id='s0',
+               pred_instances=[dict(scan_id='s0', label_id=np.int64(i + 2), conf=np.float32(0.25 * (i + 1)),
+                                    pred_mask=rle_encode(m)) for i, m in enumerate(masks)])
+    names = bench.dump_outputs(str(tmp_path / 'a'), res)
+    bench.dump_outputs(str(tmp_path / 'b'), res)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(k + '.npy' for k in names)
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    load = lambda k: np.load(tmp_path / 'a' / (k + '.npy'))
+    assert np.array_equal(load('semantic_preds'), res['semantic_preds']) and load('semantic_preds').dtype == np.float64
+    assert np.array_equal(load('offset_preds'), res['offset_preds']) and load('offset_preds').dtype == np.float32
+    assert load('pred_instances_label_id').tolist() == [2, 3, 4]
+    assert load('pred_instances_conf').tolist() == [0.25, 0.5, 0.75]
+    assert load('pred_instances_mask_points').tolist() == [float(m.sum()) for m in masks]
+    idx = load('pred_instances_mask_sample_index').astype(np.int64)
+    assert len(idx) == 16384 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(load('pred_instances_mask_sample'), np.stack([rle_decode(rle_encode(m))[idx] for m in masks]))

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for rep in 1 2; do
 for v in "$@"; do
-  env $v python $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-legs 2>/dev/null | python -c "
+  env $v python $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-legs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('$v', 'conv ms/scan', r['kernel_ms_per_scan'], 'frac', r['frac'], 'ms/step', d['ms_per_step'], 'latency', d['latency_ms'])"

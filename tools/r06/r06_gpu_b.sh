@@ -16,6 +16,6 @@ done
 rm -rf /tmp/prof_scan
 timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d /tmp/prof_scan -o r -- python $R/tools/scan_only.py 16 150000 scannet > /dev/null 2>&1
 python $R/tools/scan_sequence.py /tmp/prof_scan $OUT/r06b_scan_scannet pointwise_heads_kernel
-timeout 600 python $R/bench.py --no-cpu-baseline --no-legs > $OUT/r06b_bench.json 2> $OUT/r06b_bench.err
-timeout 600 python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-legs > $OUT/r06b_bench20.json 2>> $OUT/r06b_bench.err
+timeout 600 python $R/bench.py --full --no-cpu-baseline --no-legs > $OUT/r06b_bench.json 2> $OUT/r06b_bench.err
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-legs > $OUT/r06b_bench20.json 2>> $OUT/r06b_bench.err
 echo done

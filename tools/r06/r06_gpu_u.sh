@@ -5,7 +5,7 @@ cd $R
 timeout 600 python -m pytest tests/test_data_gpu.py -m gpu -x -q 2>&1 | tail -2 > $OUT/r06u_summary.txt
 cd /tmp && export TMPDIR=/tmp
 for LD in 1 2; do
-SG_BENCH_LOADERS=$LD python $R/bench.py --no-cpu-baseline > $OUT/r06u_bench.json 2> $OUT/r06u_bench.err
+SG_BENCH_LOADERS=$LD python $R/bench.py --full --no-cpu-baseline > $OUT/r06u_bench.json 2> $OUT/r06u_bench.err
 python -c "
 import json
 d=json.loads(open('$OUT/r06u_bench.json').read().strip().splitlines()[-1])
