@@ -862,6 +862,54 @@ int sg_eval_intersections(const int32_t *run_start, const int64_t *run_off, cons
                           int n_runs, int64_t total_points, const int32_t *gt_slot, int n_pred,
                           int n_slots, int32_t *counts, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Point-wise and panoptic evaluation.  Label arrays are typed by a kind: SG_EVAL_I32, SG_EVAL_I64
+ * or SG_EVAL_U32 (int32 storage read as unsigned), each buffer 16-byte aligned; offsets are
+ * float32 [n, 3].  Outputs accumulate (the caller zeroes them once), so chunks of scans add up.
+ * *flags gets SG_EVAL_BAD_* bits for inputs the kernels cannot represent exactly; the caller then
+ * evaluates on the host.
+ * ---------------------------------------------------------------------------------------- */
+#define SG_EVAL_I32 0
+#define SG_EVAL_I64 1
+#define SG_EVAL_U32 2
+#define SG_EVAL_MAX_CLASSES 1024
+#define SG_EVAL_BAD_GT 1      /* a valid gt class outside [0, n_classes) */
+#define SG_EVAL_BAD_PRED 2    /* panoptic: a prediction outside [0, 2**32) */
+#define SG_EVAL_BAD_INST 4    /* panoptic: an instance label whose y_inst does not fit 31 bits */
+
+/* evaluate_semantic_acc / evaluate_semantic_miou / evaluate_offset_mae
+ * (softgroup/evaluation/point_wise_eval.py:4-44) and PanopticEval's seen / correct / positive
+ * (softgroup/evaluation/panoptic_eval.py:58-62): over the points with gt != ignore_label,
+ *   tallies[c] += seen, tallies[n_classes + c] += positive, tallies[2 n_classes + c] += correct
+ * (pred class = pred, or pred & 0xFFFF when `panoptic`; predictions outside [0, n_classes) count
+ * nowhere).  With offset_pred non-null also, over the points with inst != ignore_label,
+ *   *offset_sum += sum of |offset_gt - offset_pred| (float32 differences, fp64 sum in a fixed
+ *   order: bitwise repeatable), *offset_count += number of those points.
+ * pred NULL: offsets only (gt and tallies unused).
+ * ws: sg_eval_tally_workspace_bytes(n_points) bytes (only used with offsets). */
+size_t sg_eval_tally_workspace_bytes(int64_t n_points);
+int sg_eval_class_tally(const void *pred, int pred_kind, const void *gt, int gt_kind, int64_t n_points,
+                        int64_t ignore_label, int panoptic, int n_classes, uint64_t *tallies,
+                        const void *inst, int inst_kind, const float *offset_pred, const float *offset_gt,
+                        double *offset_sum, uint64_t *offset_count, int32_t *flags, void *ws, size_t ws_bytes,
+                        sg_stream_t stream);
+
+/* PanopticEval.evaluate_single's segment matching (softgroup/evaluation/panoptic_eval.py:24-166)
+ * for n_scans scans laid end to end (scan s = points scan_off[s] .. scan_off[s+1]-1, n_scans <=
+ * 65535, n_points < 2**30).  Over the points with sem != ignore_label: pred segments (scan, pred & 0xFFFF,
+ * pred + 1), gt segments (scan, sem, y) with y = (inst == ignore_label ? -1 : inst) + 2 > 0, and their
+ * intersections.  A pair with I / U > 0.5 (double) is a TP: its row (scan << 16 | cl, y << 32 | x,
+ * I, U) goes to tp_rows[4 * r] (capacity n_points rows); *tp_count is set to the number of rows.
+ * Unmatched segments of at least min_points points add to fp_fn[cl] (pred) and fp_fn[n_classes + cl]
+ * (gt).
+ * ws: sg_eval_panoptic_workspace_bytes(n_points) bytes. */
+size_t sg_eval_panoptic_workspace_bytes(int64_t n_points);
+int sg_eval_panoptic_segments(const void *pred, int pred_kind, const void *sem, int sem_kind,
+                              const void *inst, int inst_kind, const int64_t *scan_off, int n_scans,
+                              int64_t n_points, int64_t ignore_label, int n_classes, int64_t min_points,
+                              uint64_t *fp_fn, int64_t *tp_rows, uint64_t *tp_count, int32_t *flags,
+                              void *ws, size_t ws_bytes, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,12 @@ SIGNATURES = {
     'sg_scan_arena_bytes': (_sz, [_vp, _i, _i]),
     'sg_scan_forward': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     'sg_eval_intersections': (_i, [_vp, _vp, _vp, _i, _i64, _vp, _i, _i, _vp, _vp]),
+    'sg_eval_tally_workspace_bytes': (_sz, [_i64]),
+    'sg_eval_class_tally': (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _sz, _vp]),
+    'sg_eval_panoptic_workspace_bytes': (_sz, [_i64]),
+    'sg_eval_panoptic_segments': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i64, _i64, _i, _i64, _vp, _vp, _vp,
+                                       _vp, _vp, _sz, _vp]),
     'sg_bn_relu_f32': (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'sg_gather_rows_f32': (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     'sg_gather_rows_i64idx_f32': (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
