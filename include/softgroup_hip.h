@@ -910,6 +910,65 @@ int sg_eval_panoptic_segments(const void *pred, int pred_kind, const void *sem, 
                               uint64_t *fp_fn, int64_t *tp_rows, uint64_t *tp_count, int32_t *flags,
                               void *ws, size_t ws_bytes, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training-time data transform (softgroup/data/custom.py:52-194, data/kitti.py:78-118,
+ * data/s3dis.py:31-41).  Points are [n, 3] row-major; labels int64.  `stats` receives 9 uint64
+ * order-preserving keys of float64 values -- max |x|, min x, max x per axis -- decoded by the caller
+ * (key with the top bit set: bits = key ^ 2^63; otherwise bits = ~key).
+ * ---------------------------------------------------------------------------------------- */
+/* dataAugment's product (custom.py:92-111): xyz_middle = (float32(xyz * scale_factor) if has_scale) @ m
+ * in float64 (m_host: 9 doubles, row-major, read on the host); work = xyz_middle * work_scale (/ down
+ * when down != 1: kitti.py:96); stats of work. */
+int sg_train_augment(const float *xyz, int64_t n, int has_scale, float scale_factor, const double *m_host,
+                     double work_scale, double down, double *xyz_middle, double *work, uint64_t *stats,
+                     sg_stream_t stream);
+/* elastic's six scipy.ndimage.convolve passes with the [1,1,1]/3 box along x, y, z, x, y, z, zero
+ * boundary (custom.py:53-64), on n_grids float32 grids [b0, b1, b2] laid end to end, in place (tmp: the
+ * same size); each pass sums in float64 and rounds to float32. */
+int sg_train_blur(float *grids, float *tmp, int b0, int b1, int b2, int n_grids, sg_stream_t stream);
+/* elastic's interpolation and update (custom.py:65-74): work += g(work) * mag, g = trilinear sampling in
+ * float64 of the three blurred grids on the axes linspace(-(b-1) gran, (b-1) gran, b), 0 outside, as
+ * scipy's RegularGridInterpolator sums it; stats of the result. */
+int sg_train_elastic(double *work, int64_t n, const float *grids, int b0, int b1, int b2, double gran, double mag,
+                     uint64_t *stats, sg_stream_t stream);
+/* crop's test (custom.py:113-127) for k <= 16 candidates cand_host[6 j ..] = (offset xyz, spatial shape
+ * xyz): counts[j] = #points p with t + offset >= 0 and < shape on every axis, t = (work * down) - min
+ * (min_host: 3 doubles; custom.py:143, kitti.py:101-103). */
+int sg_train_crop_count(const double *work, int64_t n, double down, const double *min_host,
+                        const double *cand_host, int k, uint64_t *counts, sg_stream_t stream);
+/* The kept points in order (custom.py:155-160, 184): coord = trunc(t + offset) (t as above; every point
+ * kept and no offset when crop_host is NULL), xyz_middle, feat [n, c] + noise[c] (float32; noise may be
+ * NULL), semantic and instance labels; at most out_cap rows are written.  *kept = number of kept points.
+ * ws: sg_train_compact_workspace_bytes(n) bytes. */
+size_t sg_train_compact_workspace_bytes(int64_t n);
+int sg_train_compact(const double *work, const double *xyz_middle, const float *feat, int c, const float *noise,
+                     const int64_t *sem, const int64_t *inst, int64_t n, double down, const double *min_host,
+                     const double *crop_host, int64_t out_cap, int64_t *coord, double *xyz_middle_out,
+                     float *feat_out, int64_t *sem_out, int64_t *inst_out, int32_t *kept, void *ws,
+                     size_t ws_bytes, sg_stream_t stream);
+/* S3DISDataset.load's subsample (s3dis.py:31-41): rows idx[0..m) of xyz (float32 [n, 3]), feat
+ * (float32 [n, c]) and the labels. */
+int sg_train_gather(const int64_t *idx, int64_t m, const float *xyz, const float *feat, int c, const int64_t *sem,
+                    const int64_t *inst, float *xyz_out, float *feat_out, int64_t *sem_out, int64_t *inst_out,
+                    sg_stream_t stream);
+/* The set of instance ids present (getCroppedInstLabel, custom.py:129-136 / kitti.py:78-90): labels !=
+ * ignore, each once, to out[1 ..] in no particular order, their number to out[0] (only the first cap
+ * are stored; cap <= 8192).  ws: sg_train_id_set_workspace_bytes() bytes. */
+size_t sg_train_id_set_workspace_bytes(void);
+int sg_train_id_set(const int64_t *labels, int64_t n, int64_t ignore, int64_t *out, int cap, void *ws,
+                    size_t ws_bytes, sg_stream_t stream);
+/* The relabel itself: labels equal to sorted_ids[j] become mapped[j] (k ascending ids), in place. */
+int sg_train_remap(int64_t *labels, int64_t n, const int64_t *sorted_ids, const int64_t *mapped, int k,
+                   sg_stream_t stream);
+/* getInstanceInfo (custom.py:76-90) for dense ids 0..k-1: pointnum, cls = semantic label of the first
+ * point - cls_shift (-100 kept), pt_offset = float32(mean of xyz_middle) - xyz_middle in float64
+ * (-100 - xyz_middle outside 0..k-1).  Sums are float64 in a fixed order: bitwise repeatable.
+ * ws: sg_train_instance_workspace_bytes(n, k) bytes. */
+size_t sg_train_instance_workspace_bytes(int64_t n, int k);
+int sg_train_instance_info(const double *xyz_middle, const int64_t *inst, const int64_t *sem, int64_t n, int k,
+                           int64_t cls_shift, int32_t *pointnum, int64_t *cls, double *pt_offset, void *ws,
+                           size_t ws_bytes, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

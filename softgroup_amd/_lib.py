@@ -125,6 +125,19 @@ SIGNATURES = {
     'sg_bn_relu_f32': (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'sg_gather_rows_f32': (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     'sg_gather_rows_i64idx_f32': (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    'sg_train_augment': (_i, [_vp, _i64, _i, _f, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    'sg_train_blur': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'sg_train_elastic': (_i, [_vp, _i64, _vp, _i, _i, _i, C.c_double, C.c_double, _vp, _vp]),
+    'sg_train_crop_count': (_i, [_vp, _i64, C.c_double, _vp, _vp, _i, _vp, _vp]),
+    'sg_train_compact_workspace_bytes': (_sz, [_i64]),
+    'sg_train_compact': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, C.c_double, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _sz, _vp]),
+    'sg_train_gather': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sg_train_id_set_workspace_bytes': (_sz, []),
+    'sg_train_id_set': (_i, [_vp, _i64, _i64, _vp, _i, _vp, _sz, _vp]),
+    'sg_train_remap': (_i, [_vp, _i64, _vp, _vp, _i, _vp]),
+    'sg_train_instance_workspace_bytes': (_sz, [_i64, _i]),
+    'sg_train_instance_info': (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -391,3 +391,6 @@ def prefetch_device(batches, collate=None, depth=1, device='cuda', workers=1):
                     slot[1].synchronize()
         with _STAGING_POOL_LOCK:
             _STAGING_POOL.extend(stagings)
+
+
+from .train import TrainTransform, collate_train_device  # noqa: E402,F401
