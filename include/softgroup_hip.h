@@ -911,6 +911,46 @@ int sg_eval_panoptic_segments(const void *pred, int pred_kind, const void *sem, 
                               void *ws, size_t ws_bytes, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Axis-aligned box detection AP (tools/eval_det.py).  Coordinates are [n, 3] row-major, float32
+ * (coords_f64 = 0) or float64 (1), of all scans laid end to end.  boxes[6 o .. 6 o + 5] = (xmin ymin
+ * zmin xmax ymax zmax) of owner o in float64, exact (order-preserving integer keys); an owner without
+ * points gets NaN.  *flags gets SG_DET_BAD_COORD when an owned point has a non-finite coordinate
+ * (the caller then forms the boxes on the host: numpy's min / max propagate NaN).
+ * ---------------------------------------------------------------------------------------- */
+#define SG_DET_BAD_COORD 1
+#define SG_DET_MAX_THRESHOLDS 16
+
+/* Prediction boxes, coords[mask].min(0) / .max(0) (eval_det.py:290-297).  Masks come as runs, as for
+ * sg_eval_intersections: run r covers points run_start[r] .. run_start[r] + len(r) - 1 (global point
+ * indices) of owner run_owner[r] in [0, n_owner); run_off = exclusive prefix sum of the lengths
+ * (run_off[n_runs] = total_points). */
+int sg_det_boxes_runs(const void *coords, int coords_f64, const int64_t *run_start, const int64_t *run_off,
+                      const int32_t *run_owner, int64_t n_runs, int64_t total_points, int64_t n_owner,
+                      double *boxes, int32_t *flags, sg_stream_t stream);
+
+/* GT instance boxes, coords[instance_label == i].min(0) / .max(0) (eval_det.py:301-313), for n_scans
+ * scans (scan s = points scan_off[s] .. scan_off[s+1]-1): a point of scan s with label l in
+ * [0, owner_off[s+1] - owner_off[s]) belongs to owner owner_off[s] + l; other labels (-100) are
+ * ignored.  count[o] = points of owner o; first[o] = its lowest global point index, -1 without points
+ * (the reference takes the class from semantic_label[np.nonzero(inds)[0][0]]). */
+int sg_det_boxes_labels(const void *coords, int coords_f64, const int64_t *labels, const int64_t *scan_off,
+                        const int64_t *owner_off, int n_scans, int64_t n_points, int64_t n_owner, double *boxes,
+                        int64_t *count, int64_t *first, int32_t *flags, sg_stream_t stream);
+
+/* eval_det_cls's matching (eval_det.py:44-66, 116-146) for every class at once.  Detection d (box
+ * det_box[6 d], fp64) belongs to group det_group[d] = one (class, image); the group's GT boxes are
+ * gt_box rows group_off[g] .. group_off[g+1]-1.  det_rank[d] = d's position in its class's sorted
+ * order (host argsort).  Out: ovmax[d], jmax[d] = the first GT of the group with the strictly largest
+ * get_iou (-inf / -1 without one), and tp[k * n_det + d] = 1 when ovmax > thresholds[k] (host array,
+ * n_thresholds <= SG_DET_MAX_THRESHOLDS) and d has the lowest rank among the detections with that
+ * jmax and ovmax > thresholds[k] -- the greedy pass's TP.  ws: sg_det_match_workspace_bytes bytes. */
+size_t sg_det_match_workspace_bytes(int64_t n_gt, int n_thresholds);
+int sg_det_match(const double *det_box, const int32_t *det_group, const int32_t *det_rank, int64_t n_det,
+                 const double *gt_box, const int64_t *group_off, int64_t n_gt, const double *thresholds,
+                 int n_thresholds, double *ovmax, int64_t *jmax, uint8_t *tp, void *ws, size_t ws_bytes,
+                 sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training-time data transform (softgroup/data/custom.py:52-194, data/kitti.py:78-118,
  * data/s3dis.py:31-41).  Points are [n, 3] row-major; labels int64.  `stats` receives 9 uint64
  * order-preserving keys of float64 values -- max |x|, min x, max x per axis -- decoded by the caller
