@@ -1009,6 +1009,29 @@ int sg_train_instance_info(const double *xyz_middle, const int64_t *inst, const 
                            int64_t cls_shift, int32_t *pointnum, int64_t *cls, double *pt_offset, void *ws,
                            size_t ws_bytes, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Test-time data transform (transform_test, custom.py:162-168, with getCroppedInstLabel and getInstanceInfo,
+ * :170-194): sg_train_augment with the fixed rotation and no scale, sg_train_compact keeping every point,
+ * sg_train_id_set / sg_train_remap and sg_train_instance_info, plus the entries below.
+ * ---------------------------------------------------------------------------------------- */
+/* S3DIS x4_split, pass 1 (s3dis.py:55-65): xyz_middle = xyz @ m in float64 (m_host as sg_train_augment's);
+ * stats[3 b + a] = key of min(xyz_middle * scale) over piece b (points i with i % 4 == b) and axis a (keys as
+ * above); stats[12] = 1 when some xyz_middle * scale is not finite, else 0. */
+int sg_test_x4_minima(const float *xyz, int64_t n, const double *m_host, double scale, uint64_t *stats,
+                      sg_stream_t stream);
+/* S3DIS x4_split, pass 2 (s3dis.py:62-75): point i = 4 j + b goes to row (rows of pieces 0..b-1) + j:
+ * coord = [b, trunc(xyz_middle * scale - min_host[3 b ..])] (int64 [n, 4], 16-byte aligned), xyz_middle,
+ * feat (float32 [n, c]) and both labels. */
+int sg_test_x4_split(const float *xyz, const float *feat, int c, const int64_t *sem, const int64_t *inst, int64_t n,
+                     const double *m_host, double scale, const double *min_host, int64_t *coord,
+                     double *xyz_middle, float *feat_out, int64_t *sem_out, int64_t *inst_out, sg_stream_t stream);
+/* KITTIDataset.load's label decode (kitti.py:65-72): sem = lut[word & 0xFFFF] (the remapped learning map,
+ * stuff 0..10, thing 11..18, ignore -100; INT32_MIN where the map has no key), inst = word where sem > 10,
+ * else -100.  *missing = the smallest index whose key the map lacks, all ones when there is none (the caller
+ * raises dict.__getitem__'s KeyError). */
+int sg_kitti_decode_labels(const int32_t *words, int64_t n, const int32_t *lut, int64_t *sem, int64_t *inst,
+                           uint64_t *missing, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,9 @@ SIGNATURES = {
     'sg_train_remap': (_i, [_vp, _i64, _vp, _vp, _i, _vp]),
     'sg_train_instance_workspace_bytes': (_sz, [_i64, _i]),
     'sg_train_instance_info': (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_test_x4_minima': (_i, [_vp, _i64, _vp, C.c_double, _vp, _vp]),
+    'sg_test_x4_split': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sg_kitti_decode_labels': (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -1,6 +1,7 @@
 // train_data.hip -- the training-time data transform of the reference (softgroup/data/custom.py:52-194,
 // data/kitti.py:78-118, data/s3dis.py:31-41) on gfx950: augmentation, the two elastic passes, crop counting,
-// compaction, instance relabelling and the per-instance statistics.  Built with -ffp-contract=off: every
+// compaction, instance relabelling and the per-instance statistics; at test time (custom.py:162-194) the same
+// kernels plus the S3DIS x4 split (s3dis.py:46-78) and KITTI's label decode (kitti.py:62-72).  Built with -ffp-contract=off: every
 // float64 / float32 expression below restates the numpy / scipy arithmetic operation for operation.
 //
 // Reductions: the per-axis extrema go through order-preserving uint64 keys of the float64 values and
@@ -27,6 +28,11 @@ __device__ __forceinline__ uint64_t dkey(double d) {
 struct Mat3 {
   double m[9];
 };
+
+// column a of np.matmul(p, m) for one float64 row p (dataAugment's product, custom.py:111)
+__device__ __forceinline__ double rotate(const double (&p)[3], const Mat3 &m, int a) {
+  return (p[0] * m.m[a] + p[1] * m.m[3 + a]) + p[2] * m.m[6 + a];
+}
 
 // stats[0..2] = key(max |x|), [3..5] = key(min x), [6..8] = key(max x) per axis
 __global__ void stats_init_kernel(uint64_t *stats) {
@@ -89,7 +95,7 @@ __global__ void __launch_bounds__(kBlock) augment_kernel(const float *__restrict
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const double mid = (p[0] * m.m[a] + p[1] * m.m[3 + a]) + p[2] * m.m[6 + a];
+      const double mid = rotate(p, m, a);
       xyz_middle[3 * i + a] = mid;
       double w = mid * work_scale;
       if (down != 1.0) w = w / down;
@@ -434,6 +440,185 @@ __global__ void __launch_bounds__(kBlock) inst_offset_kernel(const double *__res
   }
 }
 
+// ---- test time: transform_test's S3DIS x4 split (s3dis.py:46-78) and KITTI's label decode (kitti.py:62-72) ----
+// One thread per quad of consecutive points 4g .. 4g+3 (point i belongs to piece i % 4).
+
+// the quad's rows of a float32 [n, 3] array: three 16-byte loads when all four rows exist and `vec` (the array
+// 16-byte aligned); returns how many of the four rows exist
+__device__ __forceinline__ int load_quad(const float *__restrict__ v, int64_t n, int64_t g, bool vec,
+                                         float (&p)[12]) {
+  const int64_t i0 = 4 * g;
+  const int cnt = n - i0 >= 4 ? 4 : static_cast<int>(n - i0);
+  if (cnt == 4 && vec) {
+    const float4 *q = reinterpret_cast<const float4 *>(v + 3 * i0);
+    const float4 a = q[0], b = q[1], c = q[2];
+    p[0] = a.x, p[1] = a.y, p[2] = a.z, p[3] = a.w;
+    p[4] = b.x, p[5] = b.y, p[6] = b.z, p[7] = b.w;
+    p[8] = c.x, p[9] = c.y, p[10] = c.z, p[11] = c.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 12; ++j) p[j] = j < 3 * cnt ? v[3 * i0 + j] : 0.0f;
+  }
+  return cnt;
+}
+
+// the quad's int64 labels: two 16-byte loads when all four exist and `vec`
+__device__ __forceinline__ void load_quad_i64(const int64_t *__restrict__ v, int64_t g, int cnt, bool vec,
+                                              int64_t (&p)[4]) {
+  if (cnt == 4 && vec) {
+    const longlong2 *q = reinterpret_cast<const longlong2 *>(v + 4 * g);
+    const longlong2 a = q[0], b = q[1];
+    p[0] = a.x, p[1] = a.y, p[2] = b.x, p[3] = b.y;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = j < cnt ? v[4 * g + j] : 0;
+  }
+}
+
+__global__ void x4_stats_init_kernel(uint64_t *stats) {
+  const int i = threadIdx.x;
+  if (i < 13) stats[i] = i < 12 ? ~0ULL : 0ULL;
+}
+
+// pass 1: key(min of xyz_middle * scale) per piece b and axis a -> stats[3 b + a]; stats[12] = 1 when a value
+// is not finite (the caller then leaves the scan to the host)
+__global__ void __launch_bounds__(kBlock) x4_minima_kernel(const float *__restrict__ xyz, int64_t n, bool vec,
+                                                          Mat3 m, double scale, uint64_t *__restrict__ stats) {
+  uint64_t mn[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) mn[j] = ~0ULL;
+  bool bad = false;
+  const int64_t quads = (n + 3) / 4;
+  for (int64_t g = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; g < quads;
+       g += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    float f[12];
+    const int cnt = load_quad(xyz, n, g, vec, f);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      if (b < cnt) {
+        const double p[3] = {f[3 * b], f[3 * b + 1], f[3 * b + 2]};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          const double w = rotate(p, m, a) * scale;
+          bad = bad || !isfinite(w);
+          const uint64_t k = dkey(w);
+          mn[3 * b + a] = k < mn[3 * b + a] ? k : mn[3 * b + a];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 12; ++j) {
+    const uint64_t lo = wave_min_u64(mn[j]);
+    if (sg::lane_id() == 0 && lo != ~0ULL)
+      atomicMin(reinterpret_cast<unsigned long long *>(stats + j), static_cast<unsigned long long>(lo));
+  }
+  const uint64_t flag = wave_max_u64(bad ? 1ULL : 0ULL);
+  if (sg::lane_id() == 0 && flag) atomicMax(reinterpret_cast<unsigned long long *>(stats + 12), 1ULL);
+}
+
+struct X4Pieces {
+  double mn[12];          // per piece and axis: min of xyz_middle * scale
+  int64_t start[4];       // first output row of each piece
+};
+
+// pass 2: point 4g + b -> row start[b] + g: coord [b, trunc(xyz_middle * scale - min_b)] (int64 [n, 4]),
+// xyz_middle, feat, labels -- the reference's concatenation order (s3dis.py:62-75)
+__global__ void __launch_bounds__(kBlock) x4_split_kernel(const float *__restrict__ xyz,
+                                                         const float *__restrict__ feat, int c,
+                                                         const int64_t *__restrict__ sem,
+                                                         const int64_t *__restrict__ inst, int64_t n, bool vec,
+                                                         Mat3 m, double scale, X4Pieces pc,
+                                                         int64_t *__restrict__ coord, double *__restrict__ mid,
+                                                         float *__restrict__ feat_out, int64_t *__restrict__ sem_out,
+                                                         int64_t *__restrict__ inst_out) {
+  const int64_t quads = (n + 3) / 4;
+  for (int64_t g = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; g < quads;
+       g += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    float f[12], fe[12];
+    int64_t ls[4], li[4];
+    const int cnt = load_quad(xyz, n, g, vec, f);
+    const bool feat3 = c == 3 && cnt == 4 && vec;
+    if (feat3) load_quad(feat, n, g, true, fe);
+    load_quad_i64(sem, g, cnt, vec, ls);
+    load_quad_i64(inst, g, cnt, vec, li);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      if (b >= cnt) continue;
+      const int64_t r = pc.start[b] + g;
+      const double p[3] = {f[3 * b], f[3 * b + 1], f[3 * b + 2]};
+      double w[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const double md = rotate(p, m, a);
+        mid[3 * r + a] = md;
+        w[a] = md * scale - pc.mn[3 * b + a];
+      }
+      longlong2 *crow = reinterpret_cast<longlong2 *>(coord + 4 * r);
+      crow[0] = make_longlong2(b, static_cast<int64_t>(w[0]));       // torch .long(): trunc
+      crow[1] = make_longlong2(static_cast<int64_t>(w[1]), static_cast<int64_t>(w[2]));
+      if (feat3) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) feat_out[3 * r + j] = fe[3 * b + j];
+      } else {
+        for (int j = 0; j < c; ++j) feat_out[r * c + j] = feat[(4 * g + b) * c + j];
+      }
+      sem_out[r] = ls[b];
+      inst_out[r] = li[b];
+    }
+  }
+}
+
+constexpr int32_t kNoKey = INT32_MIN;     // learning-map table entry of a key the map lacks
+
+// sem = lut[word & 0xFFFF] (-100 for a missing key), inst = word where sem > 10 else -100; *missing = smallest
+// index whose key is missing (left at all ones when none is)
+__global__ void __launch_bounds__(kBlock) kitti_decode_kernel(const int32_t *__restrict__ words, int64_t n, bool vec,
+                                                             const int32_t *__restrict__ lut,
+                                                             int64_t *__restrict__ sem, int64_t *__restrict__ inst,
+                                                             uint64_t *__restrict__ missing) {
+  uint64_t first = ~0ULL;
+  const int64_t quads = (n + 3) / 4;
+  for (int64_t g = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; g < quads;
+       g += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t i0 = 4 * g;
+    const int cnt = n - i0 >= 4 ? 4 : static_cast<int>(n - i0);
+    int32_t w[4];
+    if (cnt == 4 && vec) {
+      const int4 q = *reinterpret_cast<const int4 *>(words + i0);
+      w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) w[b] = b < cnt ? words[i0 + b] : 0;
+    }
+    int64_t s[4], t[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int32_t l = lut[w[b] & 0xFFFF];
+      if (l == kNoKey && b < cnt && first == ~0ULL) first = static_cast<uint64_t>(i0 + b);
+      s[b] = l == kNoKey ? -100 : l;
+      t[b] = l != kNoKey && l > 10 ? w[b] : -100;
+    }
+    if (cnt == 4 && vec) {
+      longlong2 *ps = reinterpret_cast<longlong2 *>(sem + i0), *pt = reinterpret_cast<longlong2 *>(inst + i0);
+      ps[0] = make_longlong2(s[0], s[1]);
+      ps[1] = make_longlong2(s[2], s[3]);
+      pt[0] = make_longlong2(t[0], t[1]);
+      pt[1] = make_longlong2(t[2], t[3]);
+    } else {
+      for (int b = 0; b < cnt; ++b) {
+        sem[i0 + b] = s[b];
+        inst[i0 + b] = t[b];
+      }
+    }
+  }
+  const uint64_t lo = wave_min_u64(first);
+  if (sg::lane_id() == 0 && lo != ~0ULL)
+    atomicMin(reinterpret_cast<unsigned long long *>(missing), static_cast<unsigned long long>(lo));
+}
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 inline int blocks_for(int64_t n) { return sg::grid_for(n, kBlock, 1024); }
 
 }  // namespace
@@ -577,6 +762,52 @@ int sg_train_instance_info(const double *xyz_middle, const int64_t *inst, const 
   }
   if (n) inst_offset_kernel<<<blocks_for(n), kBlock, 0, s>>>(xyz_middle, inst, n, k, mean, pt_offset);
   return sg::check_launch("sg_train_instance_info");
+}
+
+int sg_test_x4_minima(const float *xyz, int64_t n, const double *m_host, double scale, uint64_t *stats,
+                      sg_stream_t stream) {
+  SG_REQUIRE(n >= 0 && m_host && stats && (n == 0 || xyz), "sg_test_x4_minima: bad arguments");
+  hipStream_t s = sg::as_stream(stream);
+  Mat3 m;
+  for (int i = 0; i < 9; ++i) m.m[i] = m_host[i];
+  x4_stats_init_kernel<<<1, 64, 0, s>>>(stats);
+  if (n)
+    x4_minima_kernel<<<blocks_for((n + 3) / 4), kBlock, 0, s>>>(xyz, n, aligned16(xyz), m, scale, stats);
+  return sg::check_launch("sg_test_x4_minima");
+}
+
+int sg_test_x4_split(const float *xyz, const float *feat, int c, const int64_t *sem, const int64_t *inst, int64_t n,
+                     const double *m_host, double scale, const double *min_host, int64_t *coord,
+                     double *xyz_middle, float *feat_out, int64_t *sem_out, int64_t *inst_out, sg_stream_t stream) {
+  SG_REQUIRE(n >= 0 && c >= 0 && m_host && min_host &&
+                 (n == 0 || (xyz && sem && inst && coord && xyz_middle && sem_out && inst_out &&
+                             (c == 0 || (feat && feat_out)))),
+             "sg_test_x4_split: bad arguments");
+  SG_REQUIRE(aligned16(coord), "sg_test_x4_split: coord must be 16-byte aligned");
+  X4Pieces pc;
+  Mat3 m;
+  for (int i = 0; i < 9; ++i) m.m[i] = m_host[i];
+  for (int i = 0; i < 12; ++i) pc.mn[i] = min_host[i];
+  int64_t row = 0;
+  for (int b = 0; b < 4; ++b) {            // piece b holds points b, b + 4, ...: ceil((n - b) / 4) of them
+    pc.start[b] = row;
+    row += n > b ? (n - b + 3) / 4 : 0;
+  }
+  const bool vec = aligned16(xyz) && aligned16(sem) && aligned16(inst) && (c == 0 || aligned16(feat));
+  if (n)
+    x4_split_kernel<<<blocks_for((n + 3) / 4), kBlock, 0, sg::as_stream(stream)>>>(
+        xyz, feat, c, sem, inst, n, vec, m, scale, pc, coord, xyz_middle, feat_out, sem_out, inst_out);
+  return sg::check_launch("sg_test_x4_split");
+}
+
+int sg_kitti_decode_labels(const int32_t *words, int64_t n, const int32_t *lut, int64_t *sem, int64_t *inst,
+                           uint64_t *missing, sg_stream_t stream) {
+  SG_REQUIRE(n >= 0 && lut && missing && (n == 0 || (words && sem && inst)), "sg_kitti_decode_labels: bad arguments");
+  hipStream_t s = sg::as_stream(stream);
+  hipMemsetAsync(missing, 0xFF, sizeof(uint64_t), s);
+  const bool vec = aligned16(words) && aligned16(sem) && aligned16(inst);
+  if (n) kitti_decode_kernel<<<blocks_for((n + 3) / 4), kBlock, 0, s>>>(words, n, vec, lut, sem, inst, missing);
+  return sg::check_launch("sg_kitti_decode_labels");
 }
 
 }  // extern "C"

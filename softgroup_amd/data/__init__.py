@@ -135,6 +135,20 @@ def kitti_labels(label, learning_map):
     return sem, label
 
 
+KITTI_NO_KEY = np.iinfo(np.int32).min       # kitti_lut's entry for a key the learning map lacks
+
+
+def kitti_lut(learning_map):
+    """``kitti_labels``' remap as a dense int32 table over the 16-bit keys (``word & 0xFFFF``): stuff 0..10,
+    thing 11..18, unlabelled -100, ``KITTI_NO_KEY`` where the map has no key -- what the device decode
+    (sg_kitti_decode_labels) looks the words up in"""
+    lut = np.full(1 << 16, KITTI_NO_KEY, np.int32)
+    for k, v in learning_map.items():
+        if 0 <= int(k) < (1 << 16):
+            lut[int(k)] = -100 if v == 0 else (v + 10 if v < 9 else v - 9)
+    return lut
+
+
 def scan_item(xyz, rgb, semantic_label, instance_label, scale=50, scan_id='scan', cls_shift=2,
               x4_split=False, relabel='fill_gaps'):
     """What the reference's datasets return from ``__getitem__`` for one scan at TEST time
@@ -394,3 +408,4 @@ def prefetch_device(batches, collate=None, depth=1, device='cuda', workers=1):
 
 
 from .train import TrainTransform, collate_train_device  # noqa: E402,F401
+from .test import TestTransform, collate_x4_test_device  # noqa: E402,F401

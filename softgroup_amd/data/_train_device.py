@@ -32,14 +32,59 @@ def _on(dev, v, dtype):
     return t.to(dev).to(dtype).contiguous() if t.dtype != dtype else t.to(dev).contiguous()
 
 
+def relabel_ids(lab, mode, dev):
+    """getCroppedInstLabel on the device (``mode`` 'fill_gaps' or 'rank'), in place on the int64 labels: id set
+    (read back), map built on the host, one remap pass -> (number of ids, sorted ids, their new values)"""
+    lib, n = L.lib(), lab.shape[0]
+    meta = torch.empty(1 + _ID_CAP, dtype=torch.int64, device=dev)
+    ws = L.workspace(lib.sg_train_id_set_workspace_bytes(), dev)
+    L.check(lib.sg_train_id_set(L.ptr(lab), n, -100, L.ptr(meta), _ID_CAP, L.ptr(ws), ws.numel(), L.stream()),
+            'sg_train_id_set')
+    head = meta[:1 + _ID_PREFIX].cpu().numpy()       # (read-back: the instance-id set)
+    k = int(head[0])
+    if k > _ID_CAP:
+        raise L.SoftGroupHipError(f'more than {_ID_CAP} instance ids in one scan')
+    ids = head[1:1 + k] if k <= _ID_PREFIX else meta[1:1 + k].cpu().numpy()
+    ids = np.sort(ids)
+    from .train import fill_gaps_map, rank_map
+    mapped = fill_gaps_map(ids) if mode == 'fill_gaps' else rank_map(ids)
+    if k and not np.array_equal(ids, mapped):
+        d = torch.from_numpy(np.concatenate([ids, mapped]).astype(np.int64)).to(dev)
+        L.check(lib.sg_train_remap(L.ptr(lab), n, L.ptr(d[:k]), L.ptr(d[k:]), k, L.stream()), 'sg_train_remap')
+    return k, ids, mapped
+
+
+def decode_words(dev, words, lut, missing):
+    """KITTI label words (int32, a ``.label`` file) -> (semantic, instance) int64 labels on the device through
+    the learning map's table ``lut`` (data.kitti_lut, resident); ``missing`` (one int64 slot) receives the first
+    index whose key the map lacks, -1 when none does"""
+    w = _on(dev, words, torch.int32).reshape(-1)
+    n = w.shape[0]
+    sem = torch.empty(n, dtype=torch.int64, device=dev)
+    inst = torch.empty(n, dtype=torch.int64, device=dev)
+    L.check(L.lib().sg_kitti_decode_labels(L.ptr(w), n, L.ptr(lut), L.ptr(sem), L.ptr(inst), L.ptr(missing),
+                                           L.stream()), 'sg_kitti_decode_labels')
+    return sem, inst
+
+
+def raise_missing_key(words, index):
+    """dict.__getitem__'s KeyError of the reference's np.vectorize over the learning map"""
+    w = words[int(index)]
+    raise KeyError(int(w.item() if isinstance(w, torch.Tensor) else w) & 0xFFFF)
+
+
 class _DeviceRun:
     def __init__(self, tf, rs):
         self.tf, self.rs = tf, rs
+        self.words = None
         self.dev = torch.device('cuda', torch.cuda.current_device())
         self.lib = L.lib()
 
     def _stats(self, t):
-        h = _decode(t.cpu().numpy())                     # (read-back: the extrema)
+        raw = t.cpu().numpy()                            # (read-back: the extrema; slot 9: the KITTI decode's)
+        if self.words is not None and raw[9] != -1:
+            raise_missing_key(self.words, raw[9])
+        h = _decode(raw[:9])
         return h[0:3], h[3:6], h[6:9]
 
     def _ws(self, nbytes):
@@ -47,29 +92,17 @@ class _DeviceRun:
 
     def relabel(self, lab, mode):
         """getCroppedInstLabel on the device: id set (read back), map built on the host, one remap pass"""
-        lib, n = self.lib, lab.shape[0]
-        meta = torch.empty(1 + _ID_CAP, dtype=torch.int64, device=self.dev)
-        ws = self._ws(lib.sg_train_id_set_workspace_bytes())
-        L.check(lib.sg_train_id_set(L.ptr(lab), n, -100, L.ptr(meta), _ID_CAP, L.ptr(ws), ws.numel(), L.stream()),
-                'sg_train_id_set')
-        head = meta[:1 + _ID_PREFIX].cpu().numpy()       # (read-back: the instance-id set)
-        k = int(head[0])
-        if k > _ID_CAP:
-            raise L.SoftGroupHipError(f'more than {_ID_CAP} instance ids in one scan')
-        ids = head[1:1 + k] if k <= _ID_PREFIX else meta[1:1 + k].cpu().numpy()
-        ids = np.sort(ids)
-        from .train import fill_gaps_map, rank_map
-        mapped = fill_gaps_map(ids) if mode == 'fill_gaps' else rank_map(ids)
-        if k and not np.array_equal(ids, mapped):
-            d = torch.from_numpy(np.concatenate([ids, mapped]).astype(np.int64)).to(self.dev)
-            L.check(lib.sg_train_remap(L.ptr(lab), n, L.ptr(d[:k]), L.ptr(d[k:]), k, L.stream()), 'sg_train_remap')
-        return k
+        return relabel_ids(lab, mode, self.dev)[0]
 
-    def run(self, xyz, rgb, sem, inst):
+    def run(self, xyz, rgb, sem, inst, words=None):
         tf, rs, lib, dev = self.tf, self.rs, self.lib, self.dev
         xyz = _on(dev, xyz, torch.float32).reshape(-1, 3)
         n = xyz.shape[0]
         rgb = _on(dev, rgb, torch.float32).reshape(n, -1)
+        stats = torch.empty(10, dtype=torch.int64, device=dev)
+        self.words = words
+        if words is not None:                # KITTIDataset.load's decode (kitti.py:65-72); checked at the first read-back
+            sem, inst = decode_words(dev, words, tf.kitti.lut(dev), stats[9:10])
         sem = _on(dev, sem, torch.int64).reshape(n)
         inst = _on(dev, inst, torch.int64).reshape(n)
         c = rgb.shape[1]
@@ -92,7 +125,6 @@ class _DeviceRun:
         mat = np.ascontiguousarray(mat, np.float64)
         xyz_middle = torch.empty((n, 3), dtype=torch.float64, device=dev)
         work = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        stats = torch.empty(9, dtype=torch.int64, device=dev)
         L.check(lib.sg_train_augment(L.ptr(xyz), n, int(sf is not None), float(sf or 1.0), mat.ctypes.data,
                                      float(tf.scale), down, L.ptr(xyz_middle), L.ptr(work), L.ptr(stats),
                                      L.stream()), 'sg_train_augment')

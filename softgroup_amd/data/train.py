@@ -193,6 +193,33 @@ def rank_map(ids):
     return np.arange(len(ids), dtype=np.int64)
 
 
+class _KittiMap:
+    """the ``learning_map`` of semantic-kitti.yaml (as in the file) for ``label_words=``: decoded on the host by
+    ``kitti_labels``, on the device through its dense table (``kitti_lut``, one copy per device)"""
+    def __init__(self, learning_map):
+        self.map = None if learning_map is None else {int(k): int(v) for k, v in dict(learning_map).items()}
+        self._table, self._dev = None, {}
+
+    def _need(self):
+        if self.map is None:
+            raise ValueError('label_words= needs the learning_map of semantic-kitti.yaml')
+
+    def labels(self, words):
+        from . import kitti_labels
+        self._need()
+        return kitti_labels(words.cpu().numpy() if isinstance(words, torch.Tensor) else np.asarray(words), self.map)
+
+    def lut(self, dev):
+        from . import kitti_lut
+        self._need()
+        if self._table is None:
+            self._table = kitti_lut(self.map)
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = torch.from_numpy(self._table).to(dev)
+        return t
+
+
 def _relabel_numpy(lab, mode):
     """the relabel of the reference, dtype quirks included"""
     from . import _fill_gaps, _rank_ids
@@ -206,10 +233,11 @@ class TrainTransform:
     ``voxel_cfg``: ``scale``, ``spatial_shape``, ``max_npoint``, ``min_npoint`` (attributes or keys).
     ``dataset``: 'scannetv2' | 's3dis' | 'stpls3d' | 'kitti'.  ``x4_split``: S3DIS training subsample.
     ``rng``: 'device' (fast, seeded by ``(seed, index)``) or 'numpy' (the reference's stream).
-    ``device``: a GPU device, or 'cpu' for the numpy restatement."""
+    ``device``: a GPU device, or 'cpu' for the numpy restatement.  ``learning_map``: the table of
+    semantic-kitti.yaml, for raw KITTI ``label_words=`` (decoded by sg_kitti_decode_labels on the device)."""
 
     def __init__(self, voxel_cfg, dataset='scannetv2', aug_prob=1.0, x4_split=False, rng='device', seed=None,
-                 device='cuda'):
+                 device='cuda', learning_map=None):
         if dataset not in PRESETS:
             raise ValueError(f'unknown dataset {dataset!r}: one of {sorted(PRESETS)}')
         if rng not in ('device', 'numpy'):
@@ -227,6 +255,7 @@ class TrainTransform:
         self.max_npoint = _cfg(voxel_cfg, 'max_npoint')
         self.min_npoint = _cfg(voxel_cfg, 'min_npoint')
         self.trace = None          # (device='cpu': a list collects the values tested against thresholds)
+        self.kitti = _KittiMap(learning_map)
 
     @classmethod
     def from_config(cls, data_cfg, **kw):
@@ -295,13 +324,16 @@ class TrainTransform:
                 return off, shape, valid
         return None
 
-    def __call__(self, xyz, rgb, semantic_label, instance_label, scan_id='scan', index=0):
+    def __call__(self, xyz, rgb, semantic_label=None, instance_label=None, scan_id='scan', index=0, label_words=None):
+        """``label_words``: the int32 words of a KITTI ``.label`` file instead of the two label arrays"""
         rs = self._stream(index)
         if self.device.type == 'cpu':
+            if label_words is not None:
+                semantic_label, instance_label = self.kitti.labels(label_words)
             out = self._run_cpu(rs, xyz, rgb, semantic_label, instance_label)
         else:
             with torch.cuda.device(self.device):
-                out = self._run_device(rs, xyz, rgb, semantic_label, instance_label)
+                out = self._run_device(rs, xyz, rgb, semantic_label, instance_label, label_words)
         if out is None:
             return None
         return (scan_id, ) + out
@@ -372,8 +404,8 @@ class TrainTransform:
                 torch.from_numpy(inst), n_inst, pointnum, cls, torch.from_numpy(pt_offset))
 
     # ---- device --------------------------------------------------------------------------------------
-    def _run_device(self, rs, xyz, rgb, sem, inst):
-        return _DeviceRun(self, rs).run(xyz, rgb, sem, inst)
+    def _run_device(self, rs, xyz, rgb, sem, inst, words=None):
+        return _DeviceRun(self, rs).run(xyz, rgb, sem, inst, words)
 
 
 from ._train_device import _DeviceRun, collate_train_device  # noqa: E402,F401
