@@ -52,7 +52,8 @@ __device__ __forceinline__ double ld_agent(const double *p) {
 // accumulators; lanes meet in LDS in lane order; workgroup partials go to `partial` [gridDim.x][c][2] with
 // agent-scope stores; they meet in two stages (below): the last workgroup of every group of kStatGroup adds its
 // group's partials, the last group to finish adds the group sums and calls `fin(channel, sum0, sum1)`.  Every
-// order is fixed: the sums are bit-reproducible.
+// order is fixed: the sums are bit-reproducible.  `counter` (kStatCounters words) must be zero on entry and is
+// zero again when the kernel has finished.
 template <typename Elem, typename Fin>
 __device__ __forceinline__ void column_sums(int64_t rows, int c, double *partial, unsigned *counter, Elem elem,
                                             Fin fin) {
@@ -162,6 +163,9 @@ __device__ __forceinline__ void column_sums(int64_t rows, int c, double *partial
   if (tid == 0) {
     const unsigned prev = __hip_atomic_fetch_add(counter + 1 + grp, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     is_last = prev == static_cast<unsigned>(gcount - 1);
+    // every workgroup of the group has arrived: nobody touches this word again in this call.  The last one
+    // hands it back cleared, so the words are reusable by any later call in stream order (see next_counter)
+    if (is_last) __hip_atomic_store(counter + 1 + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   if (!is_last) return;
@@ -178,6 +182,7 @@ __device__ __forceinline__ void column_sums(int64_t rows, int c, double *partial
   if (tid == 0) {
     const unsigned prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     is_last = prev == static_cast<unsigned>(ngroups - 1);
+    if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (as above)
   }
   __syncthreads();
   if (!is_last) return;
@@ -396,7 +401,11 @@ struct TrainExec {
     *id = new_tensor(p, rows, c);
     return SG_OK;
   }
-  unsigned *next_counter() {      // (kStatCounters words: the top counter and one per group of workgroups)
+  // kStatCounters words: the top counter and one per group of workgroups.  The block is zeroed once per forward
+  // and every column_sums call leaves the words it used at zero again (its last workgroups clear them), so when
+  // the block is used up -- kCounters / kStatCounters = 496 calls, e.g. a 7-level net with block_reps = 10 --
+  // the walk starts over on words that are clean by the time the next call on the stream runs
+  unsigned *next_counter() {
     if (tp.counters_used + kStatCounters > kCounters) tp.counters_used = 0;
     unsigned *c = tp.counters + tp.counters_used;
     tp.counters_used += kStatCounters;
