@@ -1032,6 +1032,54 @@ int sg_test_x4_split(const float *xyz, const float *feat, int c, const int64_t *
 int sg_kitti_decode_labels(const int32_t *words, int64_t n, const int32_t *lut, int64_t *sem, int64_t *inst,
                            uint64_t *missing, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Result files of the test loop (the reference's tools/test.py --out: save_single_instance :40-54,
+ * save_gt_instance :68-77, save_panoptic_single :91-107) and their readers (tools/eval_det.py:29-32 reads the
+ * masks back with split()).  The entries produce and parse the files' BYTES in device memory; the caller
+ * moves them between pinned memory and the files.  Nothing synchronises unless stated.
+ * ---------------------------------------------------------------------------------------- */
+/* Mask text from runs: np.savetxt(path, rle_decode(rle), fmt='%d') (test.py:52-53) for masks first ..
+ * first + count - 1 of n_inst masks over `length` points, whose runs are those of sg_instance_runs (int32
+ * starts and exclusive ends, ascending and disjoint inside a mask; runs of mask k = [bounds[k], bounds[k+1])
+ * of the n_runs runs).  text (16-byte aligned, text_capacity >= count * length * 2 bytes) receives, mask after
+ * mask, '0' or '1' and '\n' per point: the file of mask first + j is text[j * length * 2 .. (j + 1) * length * 2). */
+int sg_mask_text_runs(const int32_t *starts, const int32_t *ends, const int64_t *bounds, int64_t n_runs, int n_inst,
+                      int64_t length, int first, int count, uint8_t *text, int64_t text_capacity, sg_stream_t stream);
+/* The same bytes from bit rows uint32 [n_inst, ceil(length / 32)] (sg_instances_result.bits: point i of mask k
+ * is bit i % 32 of word i / 32 of row k): the path of a caller that writes straight after the scan. */
+int sg_mask_text_bits(const uint32_t *bits, int n_inst, int64_t length, int first, int count, uint8_t *text,
+                      int64_t text_capacity, sg_stream_t stream);
+/* Decimal lines: np.savetxt(path, values, fmt='%d') (test.py:77) for int64 values[n], exact over the whole
+ * int64 range; n <= 102 261 125 (int32 text offsets).  With nyu_table (int32 [nyu_len], device) the values
+ * first take save_gt_instance's remap (test.py:70-76, floor division): sem = v // 1000, ins = v % 1000,
+ * v' = nyu_table[sem - 1] * 1000 + ins, and ins alone where sem == 0 (no table read); a negative sem - 1
+ * indexes from the end like numpy.  meta (device int64 [3]): [0] = bytes of text, [1] = values whose table
+ * index is outside the table (the reference's IndexError; their line is "0"), [2] = lines that did not fit
+ * text_capacity (dropped; 21 bytes per value always fit).  ws: sg_decimal_lines_workspace_bytes(n). */
+size_t sg_decimal_lines_workspace_bytes(int64_t n);
+int sg_decimal_lines(const int64_t *values, int64_t n, const int32_t *nyu_table, int nyu_len, uint8_t *text,
+                     int64_t text_capacity, int64_t *meta, void *ws, size_t ws_bytes, sg_stream_t stream);
+/* save_panoptic_single (test.py:91-107): out[i] = (lut[words[i] & 0xFFFF] & 0xFFFF) | (words[i] & 0xFFFF0000).
+ * lut int32 [lut_len <= 65536] is the reference's new_learning_map_inv (test.py:95-103) as a table, INT32_MIN
+ * where it has no key; classes >= lut_len have none either.  `missing` (device uint64 [2]) is scratch.
+ * SYNCHRONISES `stream`: missing_host[0] = points whose class has no entry, [1] = the first such point, [2] =
+ * its class (all ones when there is none); returns SG_ERR_UNSUPPORTED when [0] != 0 (np.vectorize raises
+ * KeyError there; out then holds the other points' words). */
+int sg_panoptic_kitti_words(const uint32_t *words, int64_t n, const int32_t *lut, int lut_len, uint32_t *out,
+                            uint64_t *missing, uint64_t *missing_host, sg_stream_t stream);
+/* Readers.  Text of "%d\n" lines (optional '-', 1 to 19 digits, '\n'; the last '\n' may be missing) ->
+ * values[line], at most `capacity` of them.  meta (device int64 [2]): [0] = lines, [1] = lines that are
+ * anything else, outside int64 or beyond capacity (the caller then parses on the host).  nbytes < 2^31.
+ * ws: sg_parse_decimal_lines_workspace_bytes(nbytes). */
+size_t sg_parse_decimal_lines_workspace_bytes(int64_t nbytes);
+int sg_parse_decimal_lines(const uint8_t *text, int64_t nbytes, int64_t *values, int64_t capacity, int64_t *meta,
+                           void *ws, size_t ws_bytes, sg_stream_t stream);
+/* Mask text ('0' | '1', '\n' per point; the last '\n' may be missing) of n = ceil(nbytes / 2) points ->
+ * flags uint8 [n] (0 | 1; may be NULL) and bits uint32 [ceil(n / 32)] (may be NULL), both 16-byte aligned
+ * like text.  meta (device int64 [2]): [0] = n, [1] = points that are anything else. */
+int sg_parse_mask_text(const uint8_t *text, int64_t nbytes, uint8_t *flags, uint32_t *bits, int64_t *meta,
+                       sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

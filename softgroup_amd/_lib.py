@@ -145,6 +145,14 @@ SIGNATURES = {
     'sg_test_x4_minima': (_i, [_vp, _i64, _vp, C.c_double, _vp, _vp]),
     'sg_test_x4_split': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sg_kitti_decode_labels': (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'sg_mask_text_runs': (_i, [_vp, _vp, _vp, _i64, _i, _i64, _i, _i, _vp, _i64, _vp]),
+    'sg_mask_text_bits': (_i, [_vp, _i, _i64, _i, _i, _vp, _i64, _vp]),
+    'sg_decimal_lines_workspace_bytes': (_sz, [_i64]),
+    'sg_decimal_lines': (_i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
+    'sg_panoptic_kitti_words': (_i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    'sg_parse_decimal_lines_workspace_bytes': (_sz, [_i64]),
+    'sg_parse_decimal_lines': (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    'sg_parse_mask_text': (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -33,6 +33,7 @@ SOURCES = [
     ('eval_ops.hip', ['-ffp-contract=off']),
     ('det_eval.hip', ['-ffp-contract=off']),
     ('train_data.hip', ['-ffp-contract=off']),
+    ('result_io.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),
 ]
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-Wall', '-Wno-unused-function',
