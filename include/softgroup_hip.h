@@ -1075,10 +1075,74 @@ size_t sg_parse_decimal_lines_workspace_bytes(int64_t nbytes);
 int sg_parse_decimal_lines(const uint8_t *text, int64_t nbytes, int64_t *values, int64_t capacity, int64_t *meta,
                            void *ws, size_t ws_bytes, sg_stream_t stream);
 /* Mask text ('0' | '1', '\n' per point; the last '\n' may be missing) of n = ceil(nbytes / 2) points ->
- * flags uint8 [n] (0 | 1; may be NULL) and bits uint32 [ceil(n / 32)] (may be NULL), both 16-byte aligned
- * like text.  meta (device int64 [2]): [0] = n, [1] = points that are anything else. */
+ * flags uint8 [n] (0 | 1; may be NULL; 16-byte aligned like text) and bits uint32 [ceil(n / 32)] (may be NULL;
+ * stored a word at a time, so any uint32 address will do: a row of a [n_inst, ceil(n / 32)] table).
+ * meta (device int64 [2]): [0] = n, [1] = points that are anything else. */
 int sg_parse_mask_text(const uint8_t *text, int64_t nbytes, uint8_t *flags, uint32_t *bits, int64_t *meta,
                        sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Point-cloud pictures of a test run (the reference's tools/visualization.py: get_coords_color :141-231 and
+ * write_ply :234-260), csrc/viz_io.hip.  Labels, colours and the PLY's vertex text are produced in device
+ * memory; the caller reads the files, moves the text to pinned memory and writes it.  Nothing synchronises.
+ * ---------------------------------------------------------------------------------------- */
+/* The instance_pred paint (visualization.py:211-220: masks visited from the lowest score to the highest, each
+ * overwriting `inst_label[mask == 1] = i`) without the order dependence: label[i] (int32 [n]) = the mask that
+ * covers point i, is not skipped, and has the highest priority[k] (int32 [n_inst]; NULL = all equal; among equal
+ * priorities the higher index), or -100 where there is none.  skip (uint8 [n_inst], may be NULL): the masks
+ * below the confidence cut (:215-216).  pointnum[k] (int32 [n_inst]) = the whole population of mask k
+ * (`ins_pointnum[i] = mask.sum()`, :219; not what the paint leaves of it), 0 for a skipped mask.  Masks as bit
+ * rows uint32 [n_inst, ceil(n / 32)] (point i of mask k is bit i % 32 of word i / 32 of row k; bits at and beyond
+ * n are ignored) ... */
+int sg_viz_paint_bits(const uint32_t *bits, int n_inst, int64_t n, const int32_t *priority, const uint8_t *skip,
+                      int32_t *label, int32_t *pointnum, sg_stream_t stream);
+/* ... or as the runs of sg_mask_text_runs (int32 starts and exclusive ends, ascending and disjoint inside a mask,
+ * runs of mask k = [bounds[k], bounds[k+1]) of the n_runs runs); ws: sg_viz_paint_runs_workspace_bytes(n_inst, n),
+ * which holds the bit rows the runs are expanded to. */
+size_t sg_viz_paint_runs_workspace_bytes(int n_inst, int64_t n);
+int sg_viz_paint_runs(const int32_t *starts, const int32_t *ends, const int64_t *bounds, int64_t n_runs, int n_inst,
+                      int64_t n, const int32_t *priority, const uint8_t *skip, int32_t *label, int32_t *pointnum,
+                      void *ws, size_t ws_bytes, sg_stream_t stream);
+/* The instance_gt labels (visualization.py:150-151 and :186-188): label[i] (int32 [n]) = ids[i] % 1000 - 1 with
+ * numpy's floor modulo, i.e. -1 .. 998, and pointnum (int32 [999]) = the points of every label >= 0. */
+int sg_viz_gt_labels(const int64_t *ids, int64_t n, int32_t *label, int32_t *pointnum, sg_stream_t stream);
+/* The colour order of the instances (visualization.py:189 and :221, `np.argsort(ins_pointnum)[::-1]`, whose tie
+ * order numpy leaves open) with the project's rule: rank[k] (int32 [n_inst]) = the position of instance k when the
+ * instances are ordered by descending pointnum, the HIGHER index first among equal counts (a stable ascending
+ * sort read backwards).  ws: sg_viz_instance_rank_workspace_bytes(n_inst). */
+size_t sg_viz_instance_rank_workspace_bytes(int n_inst);
+int sg_viz_instance_rank(const int32_t *pointnum, int n_inst, int32_t *rank, void *ws, size_t ws_bytes,
+                         sg_stream_t stream);
+/* rgb (uint8 [n, 3]) per point, as write_ply prints it (`int(c * 255)` of `rgb / 255`, :255-257 and :277):
+ *   SG_VIZ_INPUT       from colors (float32 [n, 3]): ((c + 1) * 127.5) / 255 * 255 in float32, operation by
+ *                      operation, truncated (:152, :277, :255)
+ *   SG_VIZ_CLASS       table[cls[i]] for cls (int64 [n]) >= 0, zero below (semantic_gt, :155-158)
+ *   SG_VIZ_CLASS_WRAP  table[cls[i]], a negative class indexing from the end like numpy (semantic_pred, :164-165)
+ *   SG_VIZ_INSTANCE    table[rank[inst[i]] % k] for inst (int32 [n]) >= 0, zero below (:190-192, :222-224);
+ *                      rank int32 [n_rank]
+ * table: uint8 [k, 3].  meta (device int64 [3]): [0] = labels outside the table or the ranks (the reference's
+ * IndexError), [1] = NaN colour components (`int(nan)` raises), [2] = colour components outside 0..255, which a
+ * uint8 cannot hold (the caller's host path prints those). */
+#define SG_VIZ_INPUT 0
+#define SG_VIZ_CLASS 1
+#define SG_VIZ_CLASS_WRAP 2
+#define SG_VIZ_INSTANCE 3
+int sg_viz_colors(int mode, const float *colors, const int64_t *cls, const int32_t *inst, const int32_t *rank,
+                  int n_rank, const uint8_t *table, int k, int64_t n, uint8_t *rgb, int64_t *meta,
+                  sg_stream_t stream);
+/* write_ply's vertex lines (visualization.py:253-257) for the points with keep[i] != 0 (uint8 [n]; NULL = all;
+ * the `label != -100` filter of :227-229): "%f %f %f %d %d %d\n" of xyz (float32 [n, 3]; with offset, float32
+ * [n, 3], of xyz + offset in float32: `xyz += offset_coords`, :178) and rgb (uint8 [n, 3]), point after point.
+ * The floats are what '{:f}'.format(np.float32(x)) prints: the exact binary value rounded half to even at six
+ * decimals, "-0.000000" for -0.0 and for every negative value that rounds to zero.  meta (device int64 [4]):
+ * [0] = bytes of text, [1] = lines written, [2] = kept rows DECLINED -- a coordinate that is not finite or whose
+ * magnitude is 2^31 or more; they leave no line, and the caller formats the file on the host instead -- [3] =
+ * lines that did not fit text_capacity (69 bytes per point always fit).  n <= 29 826 160 (int32 text offsets).
+ * ws: sg_viz_ply_vertices_workspace_bytes(n). */
+size_t sg_viz_ply_vertices_workspace_bytes(int64_t n);
+int sg_viz_ply_vertices(const float *xyz, const float *offset, const uint8_t *rgb, const uint8_t *keep, int64_t n,
+                        uint8_t *text, int64_t text_capacity, int64_t *meta, void *ws, size_t ws_bytes,
+                        sg_stream_t stream);
 
 #ifdef __cplusplus
 }

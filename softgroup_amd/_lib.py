@@ -153,6 +153,15 @@ SIGNATURES = {
     'sg_parse_decimal_lines_workspace_bytes': (_sz, [_i64]),
     'sg_parse_decimal_lines': (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     'sg_parse_mask_text': (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    'sg_viz_paint_bits': (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'sg_viz_paint_runs_workspace_bytes': (_sz, [_i, _i64]),
+    'sg_viz_paint_runs': (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_viz_gt_labels': (_i, [_vp, _i64, _vp, _vp, _vp]),
+    'sg_viz_instance_rank_workspace_bytes': (_sz, [_i]),
+    'sg_viz_instance_rank': (_i, [_vp, _i, _vp, _vp, _sz, _vp]),
+    'sg_viz_colors': (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp]),
+    'sg_viz_ply_vertices_workspace_bytes': (_sz, [_i64]),
+    'sg_viz_ply_vertices': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -34,6 +34,7 @@ SOURCES = [
     ('det_eval.hip', ['-ffp-contract=off']),
     ('train_data.hip', ['-ffp-contract=off']),
     ('result_io.hip', ['-ffp-contract=off']),
+    ('viz_io.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),
 ]
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-Wall', '-Wno-unused-function',

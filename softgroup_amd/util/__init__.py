@@ -3,3 +3,5 @@ from .rle import (rle_decode, rle_encode, rle_encode_many, rle_encode_runs,  # n
                   rle_text_to_dicts)  # noqa: F401
 from .results import (load_pred_instances, read_int_lines, read_mask, save_gt_instances,  # noqa: F401
                       save_npy, save_panoptic, save_pred_instances, save_results)  # noqa: F401
+from .visualize import (colors_from_result, get_coords_color, save_visualizations,  # noqa: F401
+                        write_ply)  # noqa: F401
