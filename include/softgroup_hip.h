@@ -1144,6 +1144,81 @@ int sg_viz_ply_vertices(const float *xyz, const float *offset, const uint8_t *rg
                         uint8_t *text, int64_t text_capacity, int64_t *meta, void *ws, size_t ws_bytes,
                         sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The loss block of forward_train (softgroup/model/softgroup.py:152-255) as fused kernels, csrc/losses.hip.
+ * Everything is float32, contiguous, row-major; labels are int64.  Nothing synchronises and nothing is read
+ * back: sums and losses are device scalars, upstream gradients come as device scalars (NULL = zero).  Sums are
+ * taken in double in a fixed order (per-workgroup partials in `ws`, added by one workgroup of a second kernel;
+ * no float atomics, no arrival counters): two calls on the same inputs give the same bits.
+ * ws of the three *_fwd entries: sg_loss_reduce_workspace_bytes().  n, n_proposal or m = 0 is a valid call
+ * that gives the empty sums.  Class counts above 64 return SG_ERR_UNSUPPORTED (the caller keeps the torch form).
+ * ---------------------------------------------------------------------------------------- */
+size_t sg_loss_reduce_workspace_bytes(void);
+/* point_wise_loss (softgroup.py:152-170): F.cross_entropy(semantic_scores [n, c], semantic_labels [n], weight
+ * [c] or NULL, ignore_index = ignore_label) and the L1 offset loss over the points with instance_labels !=
+ * ignore_label (pt_offsets, pt_offset_labels [n, 3]).  out (float [6]): [0] = sum w_i nll_i, [1] = sum w_i,
+ * [2] = sum |delta| over the 3 components of the instance points, [3] = n_pos, [4] = semantic_loss = [0] / [1]
+ * (NaN when every label is ignored, like torch), [5] = offset_loss = [2] / max([3], 1) (0 without an instance
+ * point, :164-165).  Max-subtracted log-sum-exp; 1 <= c <= 64.
+ * A label that is not ignore_label and lies outside [0, c) is a device assert in torch; HERE THE ROW IS TREATED
+ * AS IGNORED (no contribution, zero gradient), so the kernels never index outside a row. */
+int sg_pointwise_loss_fwd(const float *semantic_scores, const int64_t *semantic_labels, const float *weight,
+                          int64_t ignore_label, const float *pt_offsets, const float *pt_offset_labels,
+                          const int64_t *instance_labels, int64_t n, int c, float *out, void *ws, size_t ws_bytes,
+                          sg_stream_t stream);
+/* Its backward (what autograd derives from softgroup.py:159-168).  sums = `out` of the forward; g_semantic,
+ * g_offset: device scalars.  d_scores [n, c] = g_semantic / [1] * w_i * (softmax - onehot), zero rows for ignored
+ * points; d_offsets [n, 3] = g_offset / max([3], 1) * sign(delta) on instance points (sign(0) = 0), zero elsewhere.
+ * Either output may be NULL and is then skipped (a frozen backbone). */
+int sg_pointwise_loss_bwd(const float *semantic_scores, const int64_t *semantic_labels, const float *weight,
+                          int64_t ignore_label, const float *pt_offsets, const float *pt_offset_labels,
+                          const int64_t *instance_labels, int64_t n, int c, const float *sums,
+                          const float *g_semantic, const float *g_offset, float *d_scores, float *d_offsets,
+                          sg_stream_t stream);
+/* Proposal -> class label (softgroup.py:194-222).  ious_on_cluster [n_proposal, n_gt] (finite), instance_cls
+ * [n_gt]; GTs with instance_cls == ignore_label are background and count as IoU -1 (the reference drops their
+ * columns, :195-197).  A proposal whose largest IoU reaches pos_iou_thr takes that GT (lowest column among equal
+ * IoUs, torch's max); with match_low_quality every GT whose column maximum reaches min_pos_thr also claims its
+ * best proposal (lowest row among equals), and where several GTs claim one proposal the highest GT index wins
+ * (the loop of :215-217, later overwrites earlier).  labels [n_proposal] = instance_cls of the assigned GT, or
+ * background_label.  n_gt >= 1.  ws (only with match_low_quality): sg_assign_proposals_workspace_bytes. */
+size_t sg_assign_proposals_workspace_bytes(int n_proposal);
+int sg_assign_proposals(const float *ious_on_cluster, const int64_t *instance_cls, int64_t ignore_label,
+                        float pos_iou_thr, int match_low_quality, float min_pos_thr, int64_t background_label,
+                        int n_proposal, int n_gt, int64_t *labels, void *ws, size_t ws_bytes, sg_stream_t stream);
+/* cls_loss and iou_score_loss (softgroup.py:223-224, 240-255).  cls_scores, iou_scores [n_proposal, k1] with
+ * k1 = K + 1 classes (2 <= k1 <= 64, class K = background); ious_on_pred [n_proposal, n_gt] as
+ * sg_get_mask_iou_on_pred returns it.  gt_iou [n_proposal] (output, kept for the backward) = row maximum over the
+ * foreground GTs.  out (float [6]): [0] = sum of the rows' cross entropy, [1] = sum w (iou_scores[p, label] -
+ * gt_iou)^2 with w = [label < K], [2] = num_pos = sum w, [3] = num_neg, [4] = cls_loss = [0] / n_proposal,
+ * [5] = iou_score_loss = [1] / ([2] + 1).  Rows whose label lies outside [0, K] contribute nothing. */
+int sg_proposal_loss_fwd(const float *cls_scores, const float *iou_scores, const int64_t *labels,
+                         const float *ious_on_pred, const int64_t *instance_cls, int64_t ignore_label,
+                         int n_proposal, int n_gt, int k1, float *gt_iou, float *out, void *ws, size_t ws_bytes,
+                         sg_stream_t stream);
+/* d_cls_scores = g_cls / n_proposal * (softmax - onehot); d_iou_scores = g_iou / ([2] + 1) * 2 w (s - gt_iou) in
+ * the label's column, zero in the others (whole rows are written).  Either output may be NULL. */
+int sg_proposal_loss_bwd(const float *cls_scores, const float *iou_scores, const int64_t *labels,
+                         const float *gt_iou, const float *sums, const float *g_cls, const float *g_iou,
+                         int n_proposal, int k1, float *d_cls_scores, float *d_iou_scores, sg_stream_t stream);
+/* mask_loss (softgroup.py:226-238) over the m proposal points.  mask_scores [m, k1], instance_batch_idxs int32
+ * [m] (the proposal of every point), labels [n_proposal], mask_label [m] as sg_get_mask_label returns it (-1 =
+ * ignored).  mask_sig [m] = sigmoid(mask_scores[i, labels[instance_batch_idxs[i]]]), what sg_get_mask_iou_on_pred
+ * consumes.  out (float [6]): [0] = sum of F.binary_cross_entropy's terms -(y max(log p, -100) + (1 - y)
+ * max(log(1 - p), -100)) over the points with y != -1, [1] = their number, [4] = mask_loss = [0] / ([1] + 1).
+ * p, the logarithms and the gradient are evaluated in double from the float logit: where a float sigmoid already
+ * rounds to 1 (logits of 17 to 36) the result is the float64 one, not the clamp.  A point whose proposal or class
+ * index is out of range is ignored (mask_sig 0). */
+int sg_mask_loss_fwd(const float *mask_scores, const int32_t *instance_batch_idxs, const int64_t *labels,
+                     const float *mask_label, int64_t m, int n_proposal, int k1, float *mask_sig, float *out,
+                     void *ws, size_t ws_bytes, sg_stream_t stream);
+/* d_mask_scores [m, k1]: g_mask * w (p - y) / max(p (1 - p), 1e-12) * p (1 - p) / ([1] + 1) in the class column
+ * (binary_cross_entropy's backward followed by the sigmoid's, including the zero at saturated logits), zero in
+ * the other columns; every element is written. */
+int sg_mask_loss_bwd(const float *mask_scores, const int32_t *instance_batch_idxs, const int64_t *labels,
+                     const float *mask_label, const float *sums, const float *g_mask, int64_t m, int n_proposal,
+                     int k1, float *d_mask_scores, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

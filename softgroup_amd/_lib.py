@@ -162,6 +162,15 @@ SIGNATURES = {
     'sg_viz_colors': (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp]),
     'sg_viz_ply_vertices_workspace_bytes': (_sz, [_i64]),
     'sg_viz_ply_vertices': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    'sg_loss_reduce_workspace_bytes': (_sz, []),
+    'sg_pointwise_loss_fwd': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _vp, _sz, _vp]),
+    'sg_pointwise_loss_bwd': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sg_assign_proposals_workspace_bytes': (_sz, [_i]),
+    'sg_assign_proposals': (_i, [_vp, _vp, _i64, _f, _i, _f, _i64, _i, _i, _vp, _vp, _sz, _vp]),
+    'sg_proposal_loss_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'sg_proposal_loss_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'sg_mask_loss_fwd': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'sg_mask_loss_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
 }
 
 

@@ -92,6 +92,8 @@ def _cfg(cfg, key, default=None):
 
 
 class SoftGroup(nn.Module):
+    # SG_FUSED_LOSSES=1: the loss block of forward_train on the fused kernels of csrc/losses.hip (ops/losses.py)
+    use_fused_losses = os.environ.get('SG_FUSED_LOSSES', '0') == '1'
 
     def __init__(self,
                  in_channels=3,
@@ -1094,6 +1096,11 @@ class SoftGroup(nn.Module):
         weight = None
         if self.semantic_weight:
             weight = torch.tensor(self.semantic_weight, dtype=torch.float, device=semantic_scores.device)
+        if self.use_fused_losses:
+            semantic_loss, offset_loss = ops.point_wise_loss(semantic_scores, pt_offsets, semantic_labels,
+                                                             instance_labels, pt_offset_labels, weight,
+                                                             self.ignore_label)
+            return dict(semantic_loss=semantic_loss, offset_loss=offset_loss)
         losses = dict(semantic_loss=_cross_entropy(semantic_scores, semantic_labels, weight,
                                                    self.ignore_label))
         # offset loss over the points of instances (reference softgroup.py:163-169: boolean indexing,
@@ -1120,6 +1127,17 @@ class SoftGroup(nn.Module):
         poff = proposals_offset.to(dev).int().contiguous()
         instance_pointnum = instance_pointnum.int().contiguous()
         ious_on_cluster = ops.get_mask_iou_on_cluster(pidx, poff, instance_labels, instance_pointnum)
+
+        if self.use_fused_losses:
+            labels = ops.assign_proposals(ious_on_cluster, instance_cls, self.ignore_label, _cfg(tc, 'pos_iou_thr'),
+                                          _cfg(tc, 'match_low_quality', False), _cfg(tc, 'min_pos_thr', 0),
+                                          self.instance_classes)
+            mask_label = ops.get_mask_label(pidx, poff, instance_labels, instance_cls, instance_pointnum,
+                                            ious_on_cluster, _cfg(tc, 'pos_iou_thr'))
+            return ops.instance_losses(
+                cls_scores, mask_scores, iou_scores, labels, instance_batch_idxs, mask_label, instance_cls,
+                lambda sig: ops.get_mask_iou_on_pred(pidx, poff, instance_labels, instance_pointnum, sig),
+                self.ignore_label, self.instance_classes)
 
         fg = instance_cls != self.ignore_label
         labels = _assign_proposals(ious_on_cluster, instance_cls, fg, _cfg(tc, 'pos_iou_thr'),

@@ -4,3 +4,4 @@ from .functions import (ball_query, ballquery_batch_p, bfs_cluster, bfs_cluster_
                         get_mask_iou_on_cluster, get_mask_iou_on_pred, get_mask_label,
                         global_avg_pool, octree_ball_query, sec_max, sec_mean, sec_min,
                         voxelization, voxelization_idx)
+from .losses import assign_proposals, instance_losses, point_wise_loss  # noqa: F401
