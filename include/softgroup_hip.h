@@ -1219,6 +1219,71 @@ int sg_mask_loss_bwd(const float *mask_scores, const int32_t *instance_batch_idx
                      const float *mask_label, const float *sums, const float *g_mask, int64_t m, int n_proposal,
                      int k1, float *d_mask_scores, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The optimizer step as multi-tensor kernels, csrc/optim.hip: gradient norm and clip coefficient
+ * (torch.nn.utils.clip_grad_norm_), AMP unscale / skip (torch.amp.GradScaler) and the Adam / AdamW / SGD update of
+ * torch.optim.  Parameters, gradients and states are float32 and contiguous.  Nothing synchronises and nothing is
+ * read back.
+ *
+ * table: device int64 [SG_OPTIM_TABLE_ROWS, n_tensors], one column per tensor: the device addresses of the
+ * parameter, its gradient, its two states (exp_avg, exp_avg_sq / momentum_buffer, unused) and its step counter
+ * (a float32 scalar, as torch keeps it with capturable=True), and the element count.  Tensors need no alignment
+ * beyond their 4 bytes (views at an odd element offset are fine: 16-byte accesses are used where all arrays of a
+ * tensor share their address modulo 16, scalar ones elsewhere).  chunks: device int64 [n_chunks, 3] = (tensor,
+ * first element, elements), as sg_optim_plan writes it.  There is no limit on n_tensors.  n_chunks = 0 (no
+ * tensor, or only empty ones) is a valid call that launches nothing.
+ * grad_scale, found_inf: GradScaler's device scalars or NULL (scale 1, never skipped): the gradient counts as
+ * g / grad_scale, and with *found_inf != 0 a step entry writes nothing at all -- no parameter, no state, no counter.
+ * clip_coef: device scalar or NULL (1), out + 1 of sg_optim_grad_norm.
+ * Every element is updated in double from its float32 inputs and each stored value rounded once.
+ * ---------------------------------------------------------------------------------------- */
+#define SG_OPTIM_ROW_PARAM 0
+#define SG_OPTIM_ROW_GRAD 1
+#define SG_OPTIM_ROW_STATE0 2
+#define SG_OPTIM_ROW_STATE1 3
+#define SG_OPTIM_ROW_STEP 4
+#define SG_OPTIM_ROW_COUNT 5
+#define SG_OPTIM_TABLE_ROWS 6
+/* elements per chunk (fixed) */
+int sg_optim_chunk_elems(void);
+/* HOST code.  The chunk table of tensors with counts[t] elements (host int64 [n_tensors]): tensor after tensor,
+ * every element in exactly one chunk, no chunk across two tensors, none longer than sg_optim_chunk_elems(); an
+ * empty tensor has no chunk.  Returns the number of chunks (>= 0) and writes them to chunks (host int64
+ * [chunk_capacity, 3]); chunk_capacity = 0 only counts.  Negative: SG_ERR_ARG (a negative count, a null array), or
+ * SG_ERR_WORKSPACE when chunk_capacity is not 0 and too small. */
+int64_t sg_optim_plan(const int64_t *counts, int n_tensors, int64_t *chunks, int64_t chunk_capacity);
+/* bytes of ws for sg_optim_grad_norm (the per-workgroup partial sums) */
+size_t sg_optim_workspace_bytes(void);
+/* Two launches: the L2 norm over all gradients (as g / grad_scale), summed in double in a fixed order (per-workgroup
+ * partials in ws, added by one workgroup; no float atomics, no arrival counters: two calls give the same bits).
+ * out (device float [4]): [0] = norm, [1] = clip_coef = min(1, max_norm / (norm + 1e-6)) in float32, the formula of
+ * clip_grad_norm_ (NaN stays NaN), [2] = 1 if any g / grad_scale is not finite, else 0, [3] = 0.  With n_chunks = 0
+ * nothing is launched and out keeps what it holds. */
+int sg_optim_grad_norm(const int64_t *table, int n_tensors, const int64_t *chunks, int64_t n_chunks,
+                       const float *grad_scale, float max_norm, float *out, void *ws, size_t ws_bytes,
+                       sg_stream_t stream);
+/* One launch: torch.optim.Adam (adamw = 0: g += weight_decay * p) or AdamW (adamw = 1: p *= 1 - lr * weight_decay)
+ * with g = grad / grad_scale * clip_coef, step = counter + 1:
+ *   m = m + (1 - beta1) (g - m);  v = beta2 v + (1 - beta2) g g;
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * and advances every tensor's counter.  zero_grad != 0 writes zeros to the gradient after reading it.
+ * arrive: device int32 [n_tensors], zero before the first call; every call that returns SG_OK leaves it zero
+ * (the chunks of a tensor count themselves there, the last one advances the step counter). */
+int sg_optim_adam_step(const int64_t *table, int n_tensors, const int64_t *chunks, int64_t n_chunks, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, int adamw,
+                       const float *grad_scale, const float *found_inf, const float *clip_coef, int zero_grad,
+                       int32_t *arrive, sg_stream_t stream);
+/* One launch: torch.optim.SGD.  g += weight_decay * p;  with momentum != 0: buf = g where the counter is 0 (torch's
+ * first step), else buf = momentum buf + (1 - dampening) g;  g = nesterov ? g + momentum buf : buf;  p -= lr g.
+ * buf is STATE0 (unused and may be 0 with momentum = 0).  The counter advances like Adam's. */
+int sg_optim_sgd_step(const int64_t *table, int n_tensors, const int64_t *chunks, int64_t n_chunks, double lr,
+                      double momentum, double dampening, double weight_decay, int nesterov, const float *grad_scale,
+                      const float *found_inf, const float *clip_coef, int zero_grad, int32_t *arrive,
+                      sg_stream_t stream);
+/* One launch: g *= *coef in float32 for every gradient of the table (the second half of clip_grad_norm_). */
+int sg_optim_scale_grads(const int64_t *table, int n_tensors, const int64_t *chunks, int64_t n_chunks,
+                         const float *coef, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, 'lib', os.environ.get('SG_LIB_NAME', 'libsoftgrou
 
 _lib = None
 
-_vp, _i, _f, _i64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
+_vp, _i, _f, _i64, _sz, _d = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t, C.c_double
 _pi32 = C.POINTER(C.c_int32)
 
 # name -> (restype, argtypes).  Must list every symbol of include/softgroup_hip.h
@@ -171,6 +171,13 @@ SIGNATURES = {
     'sg_proposal_loss_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'sg_mask_loss_fwd': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'sg_mask_loss_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    'sg_optim_chunk_elems': (_i, []),
+    'sg_optim_plan': (_i64, [_vp, _i, _vp, _i64]),
+    'sg_optim_workspace_bytes': (_sz, []),
+    'sg_optim_grad_norm': (_i, [_vp, _i, _vp, _i64, _vp, _f, _vp, _vp, _sz, _vp]),
+    'sg_optim_adam_step': (_i, [_vp, _i, _vp, _i64, _d, _d, _d, _d, _d, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    'sg_optim_sgd_step': (_i, [_vp, _i, _vp, _i64, _d, _d, _d, _d, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    'sg_optim_scale_grads': (_i, [_vp, _i, _vp, _i64, _vp, _vp]),
 }
 
 

@@ -36,6 +36,7 @@ SOURCES = [
     ('result_io.hip', ['-ffp-contract=off']),
     ('viz_io.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
+    ('optim.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),
 ]
 COMMON = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-Wall', '-Wno-unused-function',
