@@ -556,7 +556,7 @@ def test_row_gather_and_bn_relu_glue(C):
         np.testing.assert_allclose(out.cpu().numpy(), ref.cpu().numpy(), rtol=0, atol=1e-6)
 
 
-@pytest.mark.parametrize('n', [1, 37, 3000, 150000])
+@pytest.mark.parametrize('n', [1, 37, 3000, 150000, 600000])
 def test_octree_build_on_the_device_equals_the_host_export(n):
     """sg_octree_build (device) == sg_octree_build_host == the reference's build_and_export_octree
     (tests/golden/octree.npz pins the host build): boxes, leaf order, leaf ranges identical"""
