@@ -911,6 +911,64 @@ int sg_eval_panoptic_segments(const void *pred, int pred_kind, const void *sem, 
                               void *ws, size_t ws_bytes, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ScanNetEval on the device (softgroup/evaluation/instance_eval.py, instance_eval_util.py's
+ * get_instances): per scan RLE text -> runs -> GT table -> intersections -> pair records -> greedy
+ * matching, examples appended to a device-resident accumulator; then the curves of all
+ * (label, threshold) segments at once.  *flags gets SG_INST_* bits; nothing is truncated silently.
+ * ---------------------------------------------------------------------------------------- */
+#define SG_INST_BAD_TEXT 1       /* RLE text: a byte that is neither a digit nor white space */
+#define SG_INST_ODD_TOKENS 2     /* RLE text: an odd number of tokens */
+#define SG_INST_RUN_RANGE 4      /* RLE text: a run outside [0, length), or more mask points than points */
+#define SG_INST_BAD_GT 8         /* a gt id below 0 or >= 2**31 */
+#define SG_INST_OVERFLOW_GT 16   /* more GT instances in a scan than gt_cap */
+#define SG_INST_OVERFLOW_EX 32   /* more examples than ex_cap (totals[0] = the number needed so far) */
+#define SG_INST_NO_EXAMPLES 64   /* a label with GT and predictions but no example: the reference raises IndexError */
+#define SG_INST_MAX_THRESHOLDS 16
+#define SG_INST_SECTIONS 16
+
+/* rle_decode's text split (softgroup/util/rle.py:25-36, instance_eval.py:377) for n_masks masks of one
+ * scan: text = the masks' `counts` strings laid end to end, mask m = bytes text_off[m] .. text_off[m+1]-1
+ * (device int64 [n_masks + 1], text_off[n_masks] <= text_bytes).  Mask m's runs go to the slots from
+ * (text_off[m] + m) / 4 on, 0-based: run_start, run_len, run_pred = mask_pred[m] (m when NULL); slots
+ * without a run have length 0; run_slots >= sg_inst_rle_run_slots(text_bytes, n_masks), else
+ * SG_ERR_WORKSPACE.  vert_count[mask_pred[m]] = the mask's points.  A run that fails its check is emptied. */
+int64_t sg_inst_rle_run_slots(int64_t text_bytes, int n_masks);
+int sg_inst_rle_parse(const uint8_t *text, const int64_t *text_off, const int32_t *mask_pred, int n_masks,
+                      int64_t text_bytes, int64_t length, int32_t *run_start, int32_t *run_len, int32_t *run_pred,
+                      int64_t run_slots, int32_t *vert_count, int32_t *flags, sg_stream_t stream);
+
+/* One scan (get_instances; assign_instances_for_scan :228-309; evaluate_matches :82-139).  gts: int64 ids
+ * class * 1000 + instance.  Runs as above (slots of length 0 allowed).  pred_label[p] = evaluated label
+ * index or -1 (not evaluated), pred_vert, pred_conf (finite, no -0.0) per prediction in list order; a
+ * prediction takes part when its label >= 0 and pred_vert >= min_region.  n_labels = n_classes, or 1 for the
+ * class-agnostic form.  thresholds: host doubles, n_thr <= SG_INST_MAX_THRESHOLDS.
+ * Appends (order-preserving score key, segment << 1 | true) examples, segment = label * n_thr + threshold,
+ * at totals[0] (device int64, zero at the start of an evaluation) and adds to seg_stats [4][n_labels * n_thr]
+ * (examples, hard false negatives, has_gt, has_pred; zero at the start).
+ * ws: sg_inst_scan_workspace_bytes bytes (0 = arguments out of range: n_pred * n_points < 2**31,
+ * n_pred * (gt_cap + 1) < 2**28); section_off (host, SG_INST_SECTIONS entries, may be NULL) receives the byte
+ * offsets of the scan's tables inside ws: 0 info int32 [8] (n_gt, mask points, pairs), 1-3 gt_id / gt_label /
+ * gt_vert int32 [gt_cap], 4 gt_pair_off [gt_cap + 1], 5 pred_pair_off [n_pred + 1], 6 pred_void [n_pred],
+ * 7-10 pairs by GT then prediction (gt, pred, inter int32; iou double), 11-14 the same by prediction then GT,
+ * 15 counts int32 [n_pred][gt_cap + 1] (last column: void). */
+size_t sg_inst_scan_workspace_bytes(int64_t n_points, int n_pred, int64_t run_slots, int n_classes, int gt_cap,
+                                    int n_thr, int n_labels, int64_t *section_off);
+int sg_inst_scan_update(const int64_t *gts, int64_t n_points, const int32_t *run_start, const int32_t *run_len,
+                        const int32_t *run_pred, int64_t run_slots, const int32_t *pred_label,
+                        const int32_t *pred_vert, const double *pred_conf, int n_pred, int n_labels, int n_classes,
+                        int64_t min_region, const double *thresholds, int n_thr, int gt_cap, uint64_t *ex_key,
+                        uint32_t *ex_meta, int64_t ex_cap, int32_t *seg_stats, int64_t *totals, int32_t *flags,
+                        void *ws, size_t ws_bytes, sg_stream_t stream);
+
+/* The curves (evaluate_matches :146-199): the examples sorted by (segment, score), cumulative true count,
+ * np.unique's boundaries, precision / recall in double, AP summed in a fixed order -> ap, rc [n_seg]
+ * (0.0 for a segment with GT only, NaN without GT).  ws: sg_inst_curves_workspace_bytes bytes. */
+size_t sg_inst_curves_workspace_bytes(int64_t n_examples, int n_seg);
+int sg_inst_curves(const uint64_t *ex_key, const uint32_t *ex_meta, int64_t n_examples, const int32_t *seg_stats,
+                   int n_seg, double *ap, double *rc, int32_t *flags, void *ws, size_t ws_bytes,
+                   sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Axis-aligned box detection AP (tools/eval_det.py).  Coordinates are [n, 3] row-major, float32
  * (coords_f64 = 0) or float64 (1), of all scans laid end to end.  boxes[6 o .. 6 o + 5] = (xmin ymin
  * zmin xmax ymax zmax) of owner o in float64, exact (order-preserving integer keys); an owner without

@@ -122,6 +122,13 @@ SIGNATURES = {
     'sg_eval_panoptic_workspace_bytes': (_sz, [_i64]),
     'sg_eval_panoptic_segments': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i64, _i64, _i, _i64, _vp, _vp, _vp,
                                        _vp, _vp, _sz, _vp]),
+    'sg_inst_rle_run_slots': (_i64, [_i64, _i]),
+    'sg_inst_rle_parse': (_i, [_vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'sg_inst_scan_workspace_bytes': (_sz, [_i64, _i, _i64, _i, _i, _i, _i, _vp]),
+    'sg_inst_scan_update': (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i,
+                                 _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_inst_curves_workspace_bytes': (_sz, [_i64, _i]),
+    'sg_inst_curves': (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sg_det_boxes_runs': (_i, [_vp, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     'sg_det_boxes_labels': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     'sg_det_match_workspace_bytes': (_sz, [_i64, _i]),

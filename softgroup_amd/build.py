@@ -31,6 +31,7 @@ SOURCES = [
     ('scan_forward.hip', ['-ffp-contract=off']),
     ('heads.hip', ['-ffp-contract=off']),
     ('eval_ops.hip', ['-ffp-contract=off']),
+    ('inst_eval.hip', ['-ffp-contract=off']),
     ('det_eval.hip', ['-ffp-contract=off']),
     ('train_data.hip', ['-ffp-contract=off']),
     ('result_io.hip', ['-ffp-contract=off']),

@@ -17,6 +17,30 @@ prediction order, the duplicate-match rule, ignore proportions from void and sma
 unique-threshold PR curve with the [-0.5, 0, 0.5] step kernel), so the averages equal the
 reference's to the last bit; tests/golden/eval_golden.json pins that against the reference's own
 evaluator.
+
+``backend='device'`` (opt-in: ``evaluate(..., backend='device')``, or ``reset()`` / ``update(preds, gts)``
+per scan / ``compute()``) moves the rest to the GPU as well (csrc/inst_eval.hip).  Stages:
+
+1. RLE text -> runs (``sg_inst_rle_parse``): the host only joins a scan's ``counts`` strings; dense-array
+   masks keep using ``_runs_of``.
+2. association, per scan (``sg_inst_scan_update``): GT table from a histogram of the ids (ascending id,
+   ``np.unique``'s order), count matrix with the void column, pair records (gt, pred, inter, iou) in both
+   orders the matcher walks.
+3. matching, per scan in the same call: one work item per (label, threshold) -- the reference's
+   ``visited`` keys carry the scan id, so the greedy walk is sequential only inside (scan, label,
+   threshold) -- count walk, scan, emit walk; (score, true flag) examples, hard false negatives and the
+   has_gt / has_pred flags are appended to a device-resident accumulator.
+4. curves, once (``sg_inst_curves``): examples sorted by (segment, order-preserving score key), cumulative
+   true count, unique boundaries, precision / recall in double, AP summed in a fixed order.
+
+``update`` copies a scan's inputs through pinned staging and enqueues on the current stream; it reads
+nothing back, so the scan's evaluation overlaps the next forward.  ``compute`` reads the example count
+and the flag word (24 bytes), launches stage 4 and reads ap / rc [n_labels, 10] back; ``compute_averages``
+is the host's.  ``last_backend`` / ``last_fallback`` say what ran: duplicate scan ids, a GT id outside
+[0, 2**31), a non-finite confidence, more than 65 535 scans and the reference's IndexError case hand the
+whole evaluation to the host path; an accumulator that proves too small is detected by the kernels
+(nothing is truncated silently) and the evaluation is redone with more room from the inputs, which are
+kept by reference until ``compute``; malformed RLE text raises ValueError.
 """
 import numpy as np
 
@@ -34,9 +58,240 @@ def _runs_of(pred_mask, n_points):
     return edges[0::2], edges[1::2] - edges[0::2]
 
 
+def _host_gts(gts):
+    """gts as the host path takes them (a device tensor comes back to the host)"""
+    return gts.detach().cpu().numpy() if hasattr(gts, 'detach') else gts
+
+
+_INST_BAD_TEXT, _INST_ODD_TOKENS, _INST_RUN_RANGE, _INST_BAD_GT = 1, 2, 4, 8
+_INST_OVERFLOW_GT, _INST_OVERFLOW_EX, _INST_NO_EXAMPLES = 16, 32, 64
+
+
+class _DeviceAccumulator(object):
+    """The device backend's state between reset() and compute(): the example accumulator
+    (score keys, segment | true flag), the per-(label, threshold) statistics, the flag word -- all on
+    the device -- and the scans' inputs by reference, for the two cases in which the evaluation is
+    redone: an accumulator that proved too small (redone on the device with more room) and an input
+    the kernels do not take (handed to the host path with the reason in `fallback`)."""
+
+    MAX_SCANS = 65535
+
+    def __init__(self, ev):
+        import torch
+        if not torch.cuda.is_available() or (ev.device is not None and not str(ev.device).startswith('cuda')):
+            raise RuntimeError("ScanNetEval backend='device' needs a GPU (device=%r, torch.cuda.is_available()=%s); "
+                               "use backend='host'" % (ev.device, torch.cuda.is_available()))
+        from .. import _lib as L
+        self.L, self.torch, self.ev = L, torch, ev
+        self.dev = torch.device('cuda' if ev.device is None else ev.device)
+        self.n_classes = len(ev.valid_class_labels)
+        self.n_labels = len(ev.eval_class_labels)
+        self.n_thr = len(ev.ious)
+        self.n_seg = self.n_labels * self.n_thr
+        self.thr = np.ascontiguousarray(ev.ious, np.float64)       # the host's float64 values, passed down
+        self.min_region = int(ev.min_region_sizes[0])
+        cap = ev.device_capacity or {}
+        self.ex_cap = int(cap.get('examples', 1 << 20))
+        self.gt_cap = int(cap.get('gt', 256))
+        self.inputs, self.fallback = [], None
+        self.scan_ids = set()
+        self.grown = 0
+        self._alloc()
+
+    def _alloc(self):
+        torch = self.torch
+        self.ex_key = torch.empty(max(self.ex_cap, 1), dtype=torch.int64, device=self.dev)
+        self.ex_meta = torch.empty(max(self.ex_cap, 1), dtype=torch.int32, device=self.dev)
+        self.seg_stats = torch.zeros(4 * self.n_seg, dtype=torch.int32, device=self.dev)
+        self.meta = torch.zeros(4, dtype=torch.int64, device=self.dev)   # [0] examples, [2] flag word (int32)
+        self.stream = None
+
+    def _flags_ptr(self):
+        return self.meta.data_ptr() + 16
+
+    def _order_streams(self):
+        """the accumulator's work stays in order when the caller changes the current stream"""
+        cur = self.torch.cuda.current_stream(self.dev)
+        if self.stream is not None and self.stream != cur:
+            cur.wait_stream(self.stream)
+        self.stream = cur
+
+    # -------------------------------------------------------------- one scan
+    def update(self, preds, gts):
+        self.inputs.append((preds, gts))
+        if self.fallback is not None:
+            return
+        if len(self.inputs) > self.MAX_SCANS:
+            self.fallback = 'more than 65535 scans'
+            return
+        ids = {p.get('scan_id') for p in preds}
+        if ids & self.scan_ids:
+            self.fallback = 'duplicate scan_id'
+            return
+        self.scan_ids |= ids
+        self._enqueue(preds, gts)
+
+    def _enqueue(self, preds, gts):
+        torch, L, ev = self.torch, self.L, self.ev
+        if not torch.is_tensor(gts):
+            gts = np.asarray(gts)
+        n_points = int(gts.shape[0])
+        n_pred = len(preds)
+        label = np.full(n_pred, -1, np.int32)
+        vert = np.zeros(n_pred, np.int32)
+        conf = np.zeros(n_pred, np.float64)
+        texts, mask_pred, h_start, h_len, h_pred = [], [], [], [], []
+        for k, pred in enumerate(preds):
+            if ev.use_label:
+                if pred['label_id'] not in ev.id2label:
+                    continue
+                label[k] = int(pred['label_id']) - 1
+            else:
+                label[k] = 0
+            conf[k] = float(pred['conf'])
+            m = pred['pred_mask']
+            if isinstance(m, dict):
+                assert int(m['length']) == n_points
+                texts.append(m['counts'])
+                mask_pred.append(k)
+            else:
+                s, n = _runs_of(m, n_points)
+                h_start.append(s)
+                h_len.append(n)
+                h_pred.append(np.full(len(s), k, np.int64))
+                vert[k] = int(n.sum())
+        if not np.isfinite(conf).all():
+            self.fallback = 'non-finite confidence'
+            return
+        conf += 0.0                                            # -0.0 -> 0.0 (np.unique takes them as equal)
+        if n_pred * n_points >= 2 ** 31 or n_points >= 2 ** 31:
+            self.fallback = 'more than 2**31 prediction x point pairs in a scan'
+            return
+        try:
+            text = ''.join(texts).encode('ascii')
+        except UnicodeEncodeError:
+            raise ValueError('malformed RLE text: a character that is neither a digit nor white space')
+        n_rle, n_text = len(texts), len(text)
+        text_off = np.zeros(n_rle + 1, np.int64)
+        text_off[1:] = np.cumsum(np.array([len(t) for t in texts], np.int64))
+        n_host = int(sum(len(s) for s in h_start))
+        slots_text = int(L.lib().sg_inst_rle_run_slots(n_text, n_rle)) if n_rle else 0
+        run_slots = slots_text + n_host
+
+        # everything of the scan in ONE pinned staging buffer and one copy (the caching host allocator keeps
+        # the buffer alive until the copy has run): conf | text_off | label | vert | mask_pred | host runs | text
+        def up8(x):
+            return (x + 7) // 8 * 8
+        parts = [conf, text_off, label, vert, np.asarray(mask_pred, np.int32),
+                 np.concatenate(h_start).astype(np.int32) if n_host else np.zeros(0, np.int32),
+                 np.concatenate(h_len).astype(np.int32) if n_host else np.zeros(0, np.int32),
+                 np.concatenate(h_pred).astype(np.int32) if n_host else np.zeros(0, np.int32),
+                 np.frombuffer(text, np.uint8)]
+        offs, total = [], 0
+        for a in parts:
+            offs.append(total)
+            total += up8(a.nbytes)
+        stage = torch.empty(max(total, 8), dtype=torch.uint8, pin_memory=True)
+        view = stage.numpy()
+        for a, o in zip(parts, offs):
+            view[o:o + a.nbytes] = a.view(np.uint8)
+        blob = torch.empty(max(total, 8), dtype=torch.uint8, device=self.dev)
+        self._order_streams()
+        blob.copy_(stage, non_blocking=True)
+        base = blob.data_ptr()
+        p_conf, p_toff, p_label, p_vert, p_mpred, p_hs, p_hl, p_hp, p_text = (base + o for o in offs)
+
+        if torch.is_tensor(gts):
+            d_gts = gts.detach().reshape(-1).to(self.dev, torch.int64, non_blocking=True).contiguous()
+        else:
+            g = np.asarray(gts).reshape(-1)
+            if g.dtype.kind not in 'iu':
+                raise TypeError(f'gts must be an integer array, not {g.dtype}')
+            pin = torch.empty(max(n_points, 1), dtype=torch.int64, pin_memory=True)
+            with np.errstate(over='ignore'):
+                pin.numpy()[:n_points] = g                     # (uint64 >= 2**63 wraps negative: flagged on the device)
+            d_gts = torch.empty(max(n_points, 1), dtype=torch.int64, device=self.dev)
+            d_gts.copy_(pin, non_blocking=True)
+
+        runs = torch.empty((3, max(run_slots, 1)), dtype=torch.int32, device=self.dev)
+        if n_host:                                             # runs of dense-array masks follow the text's slots
+            src = blob[offs[5]:offs[5] + 4 * n_host].view(torch.int32), \
+                blob[offs[6]:offs[6] + 4 * n_host].view(torch.int32), \
+                blob[offs[7]:offs[7] + 4 * n_host].view(torch.int32)
+            for r in range(3):
+                runs[r, slots_text:run_slots].copy_(src[r])
+        lib, st = L.lib(), L.stream()
+        r_start, r_len, r_pred = (runs.data_ptr() + 4 * r * runs.shape[1] for r in range(3))
+        if n_rle:
+            L.check(lib.sg_inst_rle_parse(p_text, p_toff, p_mpred, n_rle, n_text, n_points, r_start, r_len, r_pred,
+                                          slots_text, p_vert, self._flags_ptr(), st), 'sg_inst_rle_parse')
+        ws_bytes = lib.sg_inst_scan_workspace_bytes(n_points, n_pred, run_slots, self.n_classes, self.gt_cap,
+                                                    self.n_thr, self.n_labels, None)
+        if ws_bytes == 0:
+            self.fallback = 'a scan too large for the device tables'
+            return
+        ws = L.workspace(ws_bytes, self.dev)
+        L.check(lib.sg_inst_scan_update(
+            d_gts.data_ptr(), n_points, r_start, r_len, r_pred, run_slots, p_label, p_vert, p_conf, n_pred,
+            self.n_labels, self.n_classes, self.min_region, self.thr.ctypes.data, self.n_thr, self.gt_cap,
+            self.ex_key.data_ptr(), self.ex_meta.data_ptr(), self.ex_cap, self.seg_stats.data_ptr(),
+            self.meta.data_ptr(), self._flags_ptr(), ws.data_ptr(), ws_bytes, st), 'sg_inst_scan_update')
+        # (stage-level tests look at the scan's tables)
+        self._last = dict(ws=ws, blob=blob, runs=runs, gts=d_gts, n_points=n_points, n_pred=n_pred,
+                          run_slots=run_slots, vert=blob[offs[3]:offs[3] + 4 * n_pred].view(torch.int32))
+
+    # -------------------------------------------------------------- all scans
+    def compute(self):
+        """-> (ap, rc) as evaluate_matches gives them, or None with self.fallback set"""
+        torch, L = self.torch, self.L
+        for _ in range(12):
+            if self.fallback is not None:
+                return None
+            self._order_streams()
+            meta = self.meta.cpu().numpy()
+            n_ex, flags = int(meta[0]), int(meta[2]) & 0xffffffff
+            if flags & (_INST_BAD_TEXT | _INST_ODD_TOKENS | _INST_RUN_RANGE):
+                what = [t for b, t in ((_INST_BAD_TEXT, 'a byte that is neither a digit nor white space'),
+                                       (_INST_ODD_TOKENS, 'an odd number of tokens'),
+                                       (_INST_RUN_RANGE, 'a run outside the scan')) if flags & b]
+                raise ValueError('malformed RLE text: ' + ', '.join(what))
+            if flags & _INST_BAD_GT:
+                self.fallback = 'gt id negative or >= 2**31'
+                return None
+            if not flags & (_INST_OVERFLOW_GT | _INST_OVERFLOW_EX):
+                break
+            # too small: the whole evaluation again with more room (the inputs were kept by reference)
+            if flags & _INST_OVERFLOW_GT:
+                self.gt_cap = min(self.gt_cap * 4, self.n_classes * 1000)
+            if flags & _INST_OVERFLOW_EX:
+                self.ex_cap = max(2 * self.ex_cap, n_ex)
+            self.grown += 1
+            self._alloc()
+            for preds, gts in self.inputs:
+                if self.fallback is None:
+                    self._enqueue(preds, gts)
+        else:
+            self.fallback = 'accumulator capacity'
+            return None
+        out = torch.empty(2 * self.n_seg, dtype=torch.float64, device=self.dev)
+        lib = L.lib()
+        ws_bytes = lib.sg_inst_curves_workspace_bytes(n_ex, self.n_seg)
+        ws = L.workspace(ws_bytes, self.dev)
+        L.check(lib.sg_inst_curves(self.ex_key.data_ptr(), self.ex_meta.data_ptr(), n_ex, self.seg_stats.data_ptr(),
+                                   self.n_seg, out.data_ptr(), out.data_ptr() + 8 * self.n_seg, self._flags_ptr(),
+                                   ws.data_ptr(), ws_bytes, L.stream()), 'sg_inst_curves')
+        res = out.cpu().numpy()
+        if int(self.meta.cpu()[2]) & _INST_NO_EXAMPLES:
+            self.fallback = 'a label with GT and predictions but no example (the reference raises IndexError)'
+            return None
+        shape = (1, self.n_labels, self.n_thr)
+        return res[:self.n_seg].reshape(shape).copy(), res[self.n_seg:].reshape(shape).copy()
+
+
 class ScanNetEval(object):
 
-    def __init__(self, class_labels, min_npoint=None, iou_type=None, use_label=True, device=None):
+    def __init__(self, class_labels, min_npoint=None, iou_type=None, use_label=True, device=None,
+                 backend=None):
         self.valid_class_labels = class_labels
         self.valid_class_ids = np.arange(len(class_labels)) + 1
         self.id2label = {int(i): n for i, n in zip(self.valid_class_ids, class_labels)}
@@ -49,6 +304,11 @@ class ScanNetEval(object):
         self.use_label = use_label
         self.eval_class_labels = self.valid_class_labels if use_label else ['class_agnostic']
         self.device = device      # None: GPU when available
+        self.backend = backend    # of the streaming form: None / 'host' or 'device'
+        self.last_backend = None  # what the last evaluation actually ran on: 'host' or 'device'
+        self.last_fallback = None  # why a 'device' evaluation was handed to the host path, or None
+        # test hook: initial capacities of the device accumulator, dict(examples=..., gt=...)
+        self.device_capacity = None
 
     # ------------------------------------------------------------------ association (per scan)
     def _count_matrix(self, starts, lens, run_pred, n_pred, gt_slot, n_slots):
@@ -253,14 +513,70 @@ class ScanNetEval(object):
                 'rc50%': np.average(rcs[0, li, o50]), 'rc25%': np.average(rcs[0, li, o25])}
         return avg
 
-    def evaluate(self, pred_list, gt_list, verbose=True):
+    def evaluate(self, pred_list, gt_list, verbose=True, backend=None):
         """pred_list: per scan a list of dict(scan_id, label_id, conf, pred_mask (RLE dict or array));
-        gt_list: per scan an array of class_id * 1000 + instance_id per point (0 = unannotated)."""
+        gt_list: per scan an array of class_id * 1000 + instance_id per point (0 = unannotated).
+        backend: None / 'host' (the path above) or 'device' (the whole evaluation in HIP)."""
+        if backend not in (None, 'host', 'device'):
+            raise ValueError(f"backend must be None, 'host' or 'device', not {backend!r}")
+        if backend == 'device':
+            self.reset(backend='device')
+            for preds, gts in zip(pred_list, gt_list):
+                self.update(preds, gts)
+            return self.compute(verbose=verbose)
+        self.last_backend, self.last_fallback = 'host', None
         matches = {}
         for i, (preds, gts) in enumerate(zip(pred_list, gt_list)):
             gt2pred, pred2gt = self.assign_instances_for_scan(preds, gts)
             matches[f'gt_{i}'] = {'gt': gt2pred, 'pred': pred2gt}
         avgs = self.compute_averages(*self.evaluate_matches(matches))
+        if verbose:
+            self.print_results(avgs)
+        return avgs
+
+    # ------------------------------------------------------------------ streaming form
+    def reset(self, backend=None):
+        """Starts an evaluation that is fed one scan at a time: reset(), update(preds, gts) per scan,
+        compute().  backend: as for evaluate (default: the constructor's)."""
+        backend = self.backend if backend is None else backend
+        if backend not in (None, 'host', 'device'):
+            raise ValueError(f"backend must be None, 'host' or 'device', not {backend!r}")
+        self._stream_backend = 'device' if backend == 'device' else 'host'
+        self._matches = {}
+        self._dev = None
+        if self._stream_backend == 'device':
+            self._dev = _DeviceAccumulator(self)
+
+    def update(self, preds, gts):
+        """One scan.  Host backend: its matches are stored.  Device backend: the scan's inputs are copied
+        through pinned staging and its kernels are enqueued on the current stream -- nothing is read back."""
+        if getattr(self, '_stream_backend', None) is None:
+            self.reset()
+        if self._dev is not None:
+            self._dev.update(preds, gts)
+        else:
+            gt2pred, pred2gt = self.assign_instances_for_scan(preds, gts)
+            self._matches[f'gt_{len(self._matches)}'] = {'gt': gt2pred, 'pred': pred2gt}
+
+    def compute(self, verbose=False):
+        """-> the averages over the scans given to update() since reset()."""
+        if getattr(self, '_stream_backend', None) is None:
+            self.reset()
+        if self._dev is not None:
+            res = self._dev.compute()
+            if res is None:                                    # handed to the host path, with the reason
+                self.last_backend, self.last_fallback = 'host', self._dev.fallback
+                matches = {}
+                for i, (preds, gts) in enumerate(self._dev.inputs):
+                    gt2pred, pred2gt = self.assign_instances_for_scan(preds, _host_gts(gts))
+                    matches[f'gt_{i}'] = {'gt': gt2pred, 'pred': pred2gt}
+                res = self.evaluate_matches(matches)
+            else:
+                self.last_backend, self.last_fallback = 'device', None
+        else:
+            self.last_backend, self.last_fallback = 'host', None
+            res = self.evaluate_matches(self._matches)
+        avgs = self.compute_averages(*res)
         if verbose:
             self.print_results(avgs)
         return avgs
