@@ -652,6 +652,42 @@ int sg_panoptic_fusion(const uint32_t *bits, int n_inst, int n_points, const int
                        void *ws, size_t ws_bytes, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Greedy mask non-maximum suppression over bit rows (csrc/mask_nms.hip).  The reference has NO counterpart:
+ * its get_instances returns one instance per (proposal, class) pair and nothing de-duplicates them.  This
+ * stage is new and opt-in (test_cfg.nms); nothing calls it unless asked.
+ *
+ * bits: uint32 [n_inst, ceil(n_points / 32)], point i of mask k = bit i % 32 of word i / 32 of row k (the rows
+ * of sg_instances_result.bits); bits at and beyond n_points are ignored.  scores float32 [n_inst], all finite;
+ * labels int32 [n_inst], NULL = class-agnostic (as class_agnostic != 0).
+ *
+ * ORDER: descending score, and among equal scores (-0.0 equals 0.0) the LOWER index first.  This is not the
+ * rule of the panoptic fusion and of the pictures, which read an ascending argsort backwards (`[::-1]`: the
+ * higher index first).
+ * LOOP: the masks are visited in that order; a mask not yet suppressed is kept and suppresses every later mask
+ * j of the order that is not yet suppressed, has the same label (unless class-agnostic) and has
+ * inter / den > thr, strictly: one IEEE double division of the two integers, den = cnt_i + cnt_j - inter for
+ * SG_NMS_IOU and min(cnt_i, cnt_j) for SG_NMS_MIN.  den == 0 suppresses nothing (an empty mask is always
+ * kept), and a suppressed mask suppresses nobody.
+ * keep uint8 [n_inst] (1 = kept) in the original index order, *n_keep (device int32) = their number.
+ * inter_out (may be NULL): int32 [n_inst, n_inst] intersections in original indices, populations on the diagonal.
+ *
+ * RANGE: n_inst <= 16384 and n_points < 2^31; beyond it the call returns SG_ERR_UNSUPPORTED and
+ * sg_mask_nms_workspace_bytes returns 0 -- nothing is truncated.  Nothing synchronises, there is no host
+ * read-back and no float atomic: two calls on the same inputs give the same bytes. */
+#define SG_NMS_IOU 0
+#define SG_NMS_MIN 1
+size_t sg_mask_nms_workspace_bytes(int n_inst, int64_t n_points);
+int sg_mask_nms(const uint32_t *bits, int n_inst, int64_t n_points, const float *scores, const int32_t *labels,
+                double thr, int measure, int class_agnostic, uint8_t *keep, int32_t *n_keep, int32_t *inter_out,
+                void *ws, size_t ws_bytes, sg_stream_t stream);
+/* Bit rows (the layout above, every word of every row written) from runs: int32 starts and exclusive ends,
+ * ascending and disjoint inside a mask, runs of mask k = [bounds[k], bounds[k+1]) of the n_runs runs -- what
+ * sg_instance_runs and sg_mask_text_runs take, and sg_inst_rle_parse's slots with ends = start + len.  The
+ * expansion sg_viz_paint_runs does (csrc/viz_io.hip). */
+int sg_mask_bits_from_runs(const int32_t *starts, const int32_t *ends, const int64_t *bounds, int64_t n_runs,
+                           int n_inst, int64_t n_points, uint32_t *bits, sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Native host driver of the grouping head and of the result extraction (csrc/scan_exec.hip): what
  * SoftGroup.forward_grouping + clusters_voxelization (softgroup/model/softgroup.py:411-480,655-709)
  * and get_instances (:537-604) do between the network's dense heads, as one C call each --

@@ -107,6 +107,9 @@ SIGNATURES = {
     'sg_rle_format_runs_host': (_i, [_vp, _vp, _vp, _i, _vp, _i64, _vp]),
     'sg_panoptic_fusion_workspace_bytes': (_sz, [_i, _i]),
     'sg_panoptic_fusion': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, C.c_double, _i, _i, _vp, _vp, _sz, _vp]),
+    'sg_mask_nms_workspace_bytes': (_sz, [_i, _i64]),
+    'sg_mask_nms': (_i, [_vp, _i, _i64, _vp, _vp, _d, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_mask_bits_from_runs': (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp]),
     'sg_scan_grouping': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'sg_scan_grouping_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'sg_scan_instances': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),

@@ -36,6 +36,7 @@ SOURCES = [
     ('train_data.hip', ['-ffp-contract=off']),
     ('result_io.hip', ['-ffp-contract=off']),
     ('viz_io.hip', ['-ffp-contract=off']),
+    ('mask_nms.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('optim.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),

@@ -324,6 +324,16 @@ static int viz_paint_bits(const char *who, const uint32_t *bits, int n_inst, int
   return check_launch(who);
 }
 
+// the expansion sg_viz_paint_runs and sg_mask_bits_from_runs share
+static void viz_runs_to_bits(const int32_t *starts, const int32_t *ends, const int64_t *bounds, int64_t n_runs,
+                             int n_inst, int64_t n, uint32_t *bits, hipStream_t stream) {
+  const int64_t words = (n + 31) / 32;
+  const int64_t total = static_cast<int64_t>(n_inst) * words;
+  if (total > 0)
+    viz_runs_to_bits_kernel<<<viz_grid(total), kVizBlock, 0, stream>>>(starts, ends, bounds, n_runs, n_inst, n, words,
+                                                                      bits);
+}
+
 }  // namespace sg
 
 using namespace sg;
@@ -355,13 +365,18 @@ int sg_viz_paint_runs(const int32_t *starts, const int32_t *ends, const int64_t 
   SG_REQUIRE(ws != nullptr && ws_bytes >= sg_viz_paint_runs_workspace_bytes(n_inst, n),
              "sg_viz_paint_runs: workspace too small");
   hipStream_t stream = as_stream(stream_);
-  const int64_t words = (n + 31) / 32;
   uint32_t *bits = static_cast<uint32_t *>(ws);
-  const int64_t total = static_cast<int64_t>(n_inst) * words;
-  if (total > 0)
-    viz_runs_to_bits_kernel<<<viz_grid(total), kVizBlock, 0, stream>>>(starts, ends, bounds, n_runs, n_inst, n, words,
-                                                                      bits);
+  viz_runs_to_bits(starts, ends, bounds, n_runs, n_inst, n, bits, stream);
   return viz_paint_bits("sg_viz_paint_runs", bits, n_inst, n, priority, skip, label, pointnum, stream);
+}
+
+int sg_mask_bits_from_runs(const int32_t *starts, const int32_t *ends, const int64_t *bounds, int64_t n_runs,
+                           int n_inst, int64_t n, uint32_t *bits, sg_stream_t stream) {
+  SG_REQUIRE(n_inst >= 0 && n >= 0 && n <= kVizMaxPoints && n_runs >= 0 && (n_inst == 0 || bounds != nullptr) &&
+                 (n_runs == 0 || (starts && ends)) && (n_inst == 0 || n == 0 || bits != nullptr),
+             "sg_mask_bits_from_runs: bad arguments (n_inst %d, n %lld)", n_inst, static_cast<long long>(n));
+  viz_runs_to_bits(starts, ends, bounds, n_runs, n_inst, n, bits, as_stream(stream));
+  return check_launch("sg_mask_bits_from_runs");
 }
 
 int sg_viz_gt_labels(const int64_t *ids, int64_t n, int32_t *label, int32_t *pointnum, sg_stream_t stream_) {

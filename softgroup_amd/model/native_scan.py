@@ -114,9 +114,11 @@ def grouping(cfg, scores, pt_offsets, coords_float, batch_idxs, point_feats):
         n_proposals=nP)
 
 
-def instances(cfg, proposals_idx, mask_scores, cls_prob, iou_scores, panoptic=None):
-    """-> (label_id int32 [n], conf float32 [n], text str, text_off list[int], panoptic_preds) of the
+def instances(cfg, proposals_idx, mask_scores, cls_prob, iou_scores, panoptic=None, nms=None):
+    """-> (label_id int32 [n], conf float32 [n], text str, text_off list[int], panoptic_preds, keep) of the
     kept instances, in the reference's order; text/offsets follow sg_rle_format_device's convention.
+    ``nms`` (a test_cfg.nms entry) also runs sg_mask_nms on the same rows (-> keep: numpy bool [n], else None);
+    the panoptic fusion sees all n instances either way.
     ``panoptic`` = dict(semantic_preds int64 CUDA [N], cls_offset, skip_iou, semantic_classes) also
     runs the panoptic fusion on the bit rows still lying in the arena (-> uint32 numpy [N], else None)."""
     lib = L.lib()
@@ -150,7 +152,12 @@ def instances(cfg, proposals_idx, mask_scores, cls_prob, iou_scores, panoptic=No
     pan = None
     if panoptic is not None:
         pan = _panoptic(lib, arena, res, n, cfg.n_points, conf, panoptic, dev)
-    return label, conf, text, text_off, pan
+    keep = None
+    if nms is not None and n:
+        from ..ops.nms import nms_keep_rows
+        keep = nms_keep_rows(arena.data_ptr() + res.bits, arena.data_ptr() + res.label_id, n, cfg.n_points, conf,
+                             nms, dev)
+    return label, conf, text, text_off, pan, keep
 
 
 def _panoptic(lib, arena, res, n, n_points, conf, p, dev):

@@ -337,12 +337,13 @@ class ScanForward:
             o = res.dense_offset[i]
             out[name] = block[o:o + nb].view(npdt).reshape(shape)
         if want_inst and 'instance' in tasks:
-            out['pred_instances'] = self._instances(batch['scan_ids'][0], res, hbuf, N)
+            out['pred_instances'] = self._instances(batch['scan_ids'][0], res, hbuf, N, arena,
+                                                    _cfg(model.test_cfg, 'nms'))
         self.last = res
         return out
 
     @staticmethod
-    def _instances(scan_id, res, hbuf, n_points):
+    def _instances(scan_id, res, hbuf, n_points, arena=None, nms=None):
         r = res.instances
         n = r.n_kept if res.stage >= 4 else 0
         if n == 0:
@@ -353,9 +354,15 @@ class ScanForward:
         conf = h[r.off_score:r.off_score + 4 * n].view(np.float32).copy()
         text = str(memoryview(h)[r.off_text:r.off_text + r.text_bytes], 'ascii')
         n_points = int(n_points)
+        kept = range(n)
+        if nms is not None:       # test_cfg.nms: sg_mask_nms on the bit rows the scan left in the arena
+            from ..ops.nms import nms_keep_rows
+            base = arena.data_ptr() + res.instances_base
+            kept = np.flatnonzero(nms_keep_rows(base + r.bits, base + r.label_id, n, n_points, conf, nms,
+                                                arena.device)).tolist()
         return [dict(scan_id=scan_id, label_id=label[k], conf=conf[k],
                      pred_mask=dict(length=n_points, counts=text[off[k]:max(off[k + 1] - 1, off[k])]))
-                for k in range(n)]
+                for k in kept]
 
 
 UE_NP = {torch.float32: np.float32, torch.float64: np.float64, torch.float16: np.float16, torch.int64: np.int64,

@@ -5,3 +5,4 @@ from .functions import (ball_query, ballquery_batch_p, bfs_cluster, bfs_cluster_
                         global_avg_pool, octree_ball_query, sec_max, sec_mean, sec_min,
                         voxelization, voxelization_idx)
 from .losses import assign_proposals, instance_losses, point_wise_loss  # noqa: F401
+from .nms import mask_bits_from_runs, mask_nms, mask_nms_numpy  # noqa: F401

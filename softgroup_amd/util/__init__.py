@@ -5,4 +5,5 @@ from .results import (load_pred_instances, read_int_lines, read_mask, save_gt_in
                       save_npy, save_panoptic, save_pred_instances, save_results)  # noqa: F401
 from .visualize import (colors_from_result, get_coords_color, save_visualizations,  # noqa: F401
                         write_ply)  # noqa: F401
+from .nms import nms_instances  # noqa: F401
 from ..optim import build_optimizer, clip_grad_norm_  # noqa: F401,E402
