@@ -389,6 +389,15 @@ int sg_spconv_set_arithmetic(int mode);
  * same order, identical results; -1 = back to the environment (SG_CONV_COMBINE). */
 int sg_spconv_set_combine(int mode);
 
+/* Lanes per node in the grouping head's list kernels (ball-query count and fill passes, the union-find,
+ * edge-record and propagation kernels of the clustering): 64 = one wave per node, the form for lists of
+ * 36-140 entries; 8 / 16 / 32 = that many lanes per node and 64 / lanes nodes per wave in lock-step, for
+ * scenes whose lists hold a handful of entries.  0 = automatic (chosen per call from the mean list
+ * length n_edges / n); a forced value below 32 means 32 for the count pass.  Results are bit-identical
+ * for every value.  Process-wide atomic; the initial value is the environment's SG_GROUP_LANES.
+ * Returns the previous value, or -1 (SG_ERR text set) for any other argument. */
+int sg_grouping_set_lanes(int lanes);
+
 /* Multi-layer conv launches ("conv chain", csrc/spconv_conv.hip): inside sg_unet_forward the layers of
  * the U-Net levels with at most SG_CONV_CHAIN_ROWS rows (default 6144) -- softgroup/model/blocks.py:82-143
  * from the strided conv into such a level down to the deepest level and back up, and a whole U-Net that

@@ -72,6 +72,7 @@ SIGNATURES = {
     'sg_spconv_set_arithmetic': (_i, [_i]),
     'sg_spconv_set_combine': (_i, [_i]),
     'sg_spconv_set_chain': (_i, [_i]),
+    'sg_grouping_set_lanes': (_i, [_i]),
     'sg_spconv_chain_stats': (_i, [_vp, _vp]),
     'sg_spconv_profile': (_i, [_i]),
     'sg_spconv_profile_read': (_i, [_vp, _vp]),

@@ -21,6 +21,7 @@
 //      exactly the order the sequential queue produces.
 #include <stdlib.h>
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -150,7 +151,7 @@ __global__ void __launch_bounds__(256) bfs_init_kernel(int n, int32_t *parent, i
   }
 }
 
-// one wave per source node u; lanes stride over list(u).
+// one lane group per source node u; its lanes stride over list(u).
 // Two passes: a cheap first pass links every node to a neighbour (bfs_hook_min_kernel; SAMPLE = 1, the
 // first kSample entries of the list through the union-find, is what unsorted lists take), the trees are
 // flattened (bfs_compress_kernel: parent[i] = root); SAMPLE = 0 then
@@ -159,20 +160,26 @@ __global__ void __launch_bounds__(256) bfs_init_kernel(int n, int32_t *parent, i
 // parent[v] instead of two pointer chases and a CAS (the single pass took 0.16 ms on the bench scene and
 // 1.19 ms on the KITTI-like sweep).  A stale root only sends the edge down the full union path.
 constexpr int kSample = 2;
-template <int SAMPLE>
+// G lanes per source node and 64 / G nodes per wave (common.h, "lane groups"): the loop over a list has no
+// cross-lane step, so the groups of a wave simply run their own trip counts; only the "any asymmetric
+// edge" vote is per group.  G = 64 is the one-wave-per-node form.
+template <int SAMPLE, int G>
 __global__ void __launch_bounds__(256) bfs_union_kernel(const int32_t *__restrict__ idx,
                                                        const int32_t *__restrict__ start_len, int n,
                                                        int lists_sorted, int radius_lists,
                                                        int32_t *parent, int32_t *asym_nodes,
                                                        int32_t *counters) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int u = blockIdx.x * 4 + wave; u < n; u += gridDim.x * 4) {
-    const int st = start_len[2 * u], ln_all = start_len[2 * u + 1];
+  constexpr int kNodes = 64 / G;      // nodes per wave
+  const int wave = threadIdx.x >> 6, lane = group_lane<G>(), sub = (threadIdx.x & 63) / G;
+  for (int u0 = (blockIdx.x * 4 + wave) * kNodes; u0 < n; u0 += gridDim.x * 4 * kNodes) {
+    const int u = u0 + sub;
+    const bool live = G == 64 || u < n;
+    const int st = live ? start_len[2 * u] : 0, ln_all = live ? start_len[2 * u + 1] : 0;
     const int ln = SAMPLE ? min(ln_all, kSample) : ln_all;
     const bool u_capped = ln_all >= kCap;
     bool any_asym = false;
-    const int ru = SAMPLE ? -1 : SG_LD(&parent[u]);      // (flattened: the root of u as of the sampling pass)
-    for (int p0 = 0; p0 < ln; p0 += 64) {
+    const int ru = SAMPLE || !live ? -1 : SG_LD(&parent[u]);      // (flattened: the root of u as of the sampling pass)
+    for (int p0 = 0; p0 < ln; p0 += G) {
       const int p = p0 + lane;
       const int v = p < ln ? idx[st + p] : u;
       bool sym = true;
@@ -193,7 +200,7 @@ __global__ void __launch_bounds__(256) bfs_union_kernel(const int32_t *__restric
       }
       any_asym |= !sym;
     }
-    if (!SAMPLE && __any(any_asym)) {
+    if (!SAMPLE && group_any<G>(any_asym)) {
       if (lane == 0) asym_nodes[atomicAdd(&counters[0], 1)] = u;
     }
   }
@@ -244,18 +251,19 @@ __global__ void __launch_bounds__(256) bfs_store_root_kernel(int n, const int32_
 
 // ---------------------------------------------------------------- B. asymmetric propagation
 // lab[] holds, at roots, the current min-ancestor label of the set; root_of[] is frozen.
+template <int G>
 __global__ void __launch_bounds__(256) bfs_propagate_kernel(const int32_t *__restrict__ idx,
                                                            const int32_t *__restrict__ start_len,
                                                            const int32_t *__restrict__ asym_nodes,
                                                            int n_asym,
                                                            const int32_t *__restrict__ root_of,
                                                            int32_t *lab, int32_t *counters) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int a = blockIdx.x * 4 + wave; a < n_asym; a += gridDim.x * 4) {
+  const int lane = group_lane<G>();
+  for (int a = (blockIdx.x * 256 + threadIdx.x) / G; a < n_asym; a += (gridDim.x * 256) / G) {
     const int u = asym_nodes[a];
     const int ru = root_of[u];
     const int st = start_len[2 * u], ln = start_len[2 * u + 1];
-    for (int p = lane; p < ln; p += 64) {
+    for (int p = lane; p < ln; p += G) {
       const int rv = root_of[idx[st + p]];
       if (rv == ru) continue;
       const int lu = SG_LD(&lab[ru]);
@@ -275,20 +283,27 @@ __global__ void __launch_bounds__(256) bfs_label_kernel(int n, const int32_t *__
   const bool valid = i < n;
   const int l = valid ? lab[root_of[i]] : -1;
   // slot = running count of the label.  Neighbouring points mostly share their label, so the
-  // lanes of a wave with equal labels are counted together: one atomic per distinct label.
-  int slot = 0;
+  // lanes of a wave with equal labels are counted together: one atomic per distinct label.  The peer
+  // search is lane arithmetic only; the leaders of all label groups then issue their atomics in ONE
+  // instruction (one round trip for the wave, not one per distinct label) and hand `base` to their lanes.
+  int rank = 0, peers = 0, my_leader = threadIdx.x & 63;
   uint64_t todo = __ballot(valid);
   const int lane = threadIdx.x & 63;
   while (todo) {
     const int leader = __ffsll(static_cast<long long>(todo)) - 1;
     const int ll = __shfl(l, leader, 64);
     const uint64_t same = __ballot(valid && l == ll) & todo;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(&size[ll], __popcll(same));
-    base = __shfl(base, leader, 64);
-    if ((same >> lane) & 1ull) slot = base + __popcll(same & ((1ull << lane) - 1ull));
+    if ((same >> lane) & 1ull) {
+      my_leader = leader;
+      peers = __popcll(same);
+      rank = __popcll(same & ((1ull << lane) - 1ull));
+    }
     todo &= ~same;
   }
+  int base = 0;
+  if (valid && lane == my_leader) base = atomicAdd(&size[l], peers);
+  base = __shfl(base, my_leader, 64);
+  const int slot = base + rank;
   if (!valid) return;
   // (cluster label, slot of the point inside its cluster, list start, list length): one 16-B
   // record per point so that the ordered emission fetches everything about a node in one load.
@@ -338,19 +353,20 @@ __global__ void __launch_bounds__(256) bfs_seed_kernel(int n, const int4 *__rest
 // cluster's claim array (0xffff = t belongs to another cluster, never claimed; saturates at 0xfffe
 // for clusters too large for the LDS array, which claim by point id instead), and its own list
 // (start, length) so that a claimed target becomes a frontier node without a second lookup.
-// One wave per source node; this is the only place that gathers node_rec[] at random.
+// G lanes per source node (64: one wave); this is the only place that gathers node_rec[] at random.
+template <int G>
 __global__ void __launch_bounds__(256) bfs_edge_rec_kernel(const int32_t *__restrict__ idx,
                                                           const int4 *__restrict__ node_rec,
                                                           const int32_t *__restrict__ cid,
                                                           const int32_t *__restrict__ seeds,
                                                           int n, int n_cluster,
                                                           int2 *__restrict__ erec) {
-  const int lane = threadIdx.x & 63;
-  for (int v = (blockIdx.x * 256 + threadIdx.x) >> 6; v < n; v += (gridDim.x * 256) >> 6) {
+  const int lane = group_lane<G>();
+  for (int v = (blockIdx.x * 256 + threadIdx.x) / G; v < n; v += (gridDim.x * 256) / G) {
     const int4 rv = node_rec[v];
     const int c = cid[rv.x];
     if (c >= n_cluster || seeds[c] != rv.x) continue;          // source not in a kept cluster
-    for (int p = lane; p < rv.w; p += 64) {
+    for (int p = lane; p < rv.w; p += G) {
       const int4 rt = node_rec[idx[rv.z + p]];
       erec[rv.z + p] = rt.x == rv.x ? make_int2(min(rt.y, 0xfffe) | (rt.w << 16), rt.z)
                                     : make_int2(0xffff, 0);
@@ -1882,11 +1898,83 @@ int bfs_count_kept_members(const void *ws, size_t ws_bytes, int n, int64_t n_edg
   return check_launch("bfs_count_kept_members");
 }
 
+// ---------------------------------------------------------------- lanes per node
+// Process-wide choice of the list kernels' lane-group width (sg_grouping_set_lanes): 0 = automatic.
+// -1 until first used: the environment's SG_GROUP_LANES is read then.
+static std::atomic<int> g_group_lanes{-1};
+static bool lanes_value_ok(int v) { return v == 0 || v == 8 || v == 16 || v == 32 || v == 64; }
+int grouping_lanes_forced() {
+  int v = g_group_lanes.load(std::memory_order_relaxed);
+  if (v >= 0) return v;
+  const char *e = getenv("SG_GROUP_LANES");
+  const int from_env = e && lanes_value_ok(atoi(e)) ? atoi(e) : 0;
+  int expected = -1;
+  g_group_lanes.compare_exchange_strong(expected, from_env, std::memory_order_relaxed);
+  return g_group_lanes.load(std::memory_order_relaxed);
+}
+// Automatic, from the mean list length (sweep over uniform clouds of 2..60 entries per list and the
+// 138-entry blob cloud: profiles/grouping_lanes.txt):
+//   * edge records and propagation gather at random and never contend: 8 lanes per node are as fast or
+//     faster up to ~24 entries per list; narrow up to kNarrowMean = 16, else one wave per node;
+//   * the union pass is different.  With 4 entries per list 8 lanes take 0.6 of the wave-per-node time, with
+//     8 entries TWICE as long (1.40 against 0.73 ms on 100 000 points in one component): eight times as many
+//     nodes in flight CAS the same few roots.  Narrow only up to kNarrowMeanUnion = 5.
+// Real rooms have 36-140 entries per list and stay on the 64-lane kernels.
+constexpr int kNarrowMean = 16;
+constexpr int kNarrowMeanUnion = 5;
+static int lanes_auto(int64_t n_edges, int n, int narrow_mean) {
+  const int f = grouping_lanes_forced();
+  if (f) return f;
+  return n > 0 && n_edges <= static_cast<int64_t>(narrow_mean) * n ? 8 : 64;
+}
+int grouping_lanes_for(int64_t n_edges, int n) { return lanes_auto(n_edges, n, kNarrowMean); }
+// launches cover n * G / 64 waves under the same 4096-workgroup cap
+static int lanes_grid(int n, int G) { return grid_for((static_cast<int64_t>(n) * G + 63) / 64, 4, 256 * 16); }
+
+template <int SAMPLE>
+static void launch_union(int G, hipStream_t stream, const int32_t *idx, const int32_t *start_len, int n, int sorted,
+                         int radius, int32_t *parent, int32_t *asym_nodes, int32_t *counters) {
+  const int grid = lanes_grid(n, G);
+  switch (G) {
+    case 8: bfs_union_kernel<SAMPLE, 8><<<grid, 256, 0, stream>>>(idx, start_len, n, sorted, radius, parent, asym_nodes, counters); break;
+    case 16: bfs_union_kernel<SAMPLE, 16><<<grid, 256, 0, stream>>>(idx, start_len, n, sorted, radius, parent, asym_nodes, counters); break;
+    case 32: bfs_union_kernel<SAMPLE, 32><<<grid, 256, 0, stream>>>(idx, start_len, n, sorted, radius, parent, asym_nodes, counters); break;
+    default: bfs_union_kernel<SAMPLE, 64><<<grid, 256, 0, stream>>>(idx, start_len, n, sorted, radius, parent, asym_nodes, counters); break;
+  }
+}
+static void launch_propagate(int G, hipStream_t stream, const int32_t *idx, const int32_t *start_len,
+                             const int32_t *asym_nodes, int n_asym, const int32_t *root_of, int32_t *lab,
+                             int32_t *counters) {
+  const int grid = lanes_grid(n_asym, G);
+  switch (G) {
+    case 8: bfs_propagate_kernel<8><<<grid, 256, 0, stream>>>(idx, start_len, asym_nodes, n_asym, root_of, lab, counters); break;
+    case 16: bfs_propagate_kernel<16><<<grid, 256, 0, stream>>>(idx, start_len, asym_nodes, n_asym, root_of, lab, counters); break;
+    case 32: bfs_propagate_kernel<32><<<grid, 256, 0, stream>>>(idx, start_len, asym_nodes, n_asym, root_of, lab, counters); break;
+    default: bfs_propagate_kernel<64><<<grid, 256, 0, stream>>>(idx, start_len, asym_nodes, n_asym, root_of, lab, counters); break;
+  }
+}
+static void launch_edge_rec(int G, hipStream_t stream, const int32_t *idx, const int4 *node_rec, const int32_t *cid,
+                            const int32_t *seeds, int n, int n_cluster, int2 *erec) {
+  const int grid = lanes_grid(n, G);
+  switch (G) {
+    case 8: bfs_edge_rec_kernel<8><<<grid, 256, 0, stream>>>(idx, node_rec, cid, seeds, n, n_cluster, erec); break;
+    case 16: bfs_edge_rec_kernel<16><<<grid, 256, 0, stream>>>(idx, node_rec, cid, seeds, n, n_cluster, erec); break;
+    case 32: bfs_edge_rec_kernel<32><<<grid, 256, 0, stream>>>(idx, node_rec, cid, seeds, n, n_cluster, erec); break;
+    default: bfs_edge_rec_kernel<64><<<grid, 256, 0, stream>>>(idx, node_rec, cid, seeds, n, n_cluster, erec); break;
+  }
+}
+
 }  // namespace sg
 
 using namespace sg;
 
 extern "C" {
+
+int sg_grouping_set_lanes(int lanes) {
+  SG_REQUIRE(lanes_value_ok(lanes), "sg_grouping_set_lanes: lanes must be 0, 8, 16, 32 or 64");
+  grouping_lanes_forced();      // (settles the environment's value first, so that it is what is returned)
+  return g_group_lanes.exchange(lanes, std::memory_order_relaxed);
+}
 
 size_t sg_bfs_workspace_bytes(int n, int64_t n_edges) {
   const size_t nn = static_cast<size_t>(n > 0 ? n : 1);
@@ -1912,25 +2000,23 @@ int sg_bfs_cluster_label(const int32_t *bq_idxs, const int32_t *start_len, int n
   *sum_npoint_host = 0;
   if (n == 0) return SG_OK;
   const int grid = (n + 255) / 256;
+  const int lanes_union = lanes_auto(n_edges, n, kNarrowMeanUnion);      // lanes per node of the list kernels
+  const int lanes = lanes_auto(n_edges, n, kNarrowMean);
   hipMemsetAsync(w.counters, 0, 64 * 4, stream);
   bfs_init_kernel<<<grid, 256, 0, stream>>>(n, w.parent, w.size, w.owner);
   static const bool one_pass = getenv("SG_BFS_ONE_PASS") != nullptr;      // developer A/B knob: round 4's single pass
   if (!one_pass) {
     static const bool sample_env = getenv("SG_BFS_SAMPLE") != nullptr;      // developer A/B knob: union-find sampling pass
     if (sample_env || !(list_flags & SG_LISTS_SORTED))
-      bfs_union_kernel<1><<<grid_for(n, 4, 256 * 16), 256, 0, stream>>>(bq_idxs, start_len, n,
-                                                                      list_flags & SG_LISTS_SORTED,
-                                                                      list_flags & SG_LISTS_RADIUS,
-                                                                      w.parent, w.asym_nodes, w.counters);
+      launch_union<1>(lanes_union, stream, bq_idxs, start_len, n, list_flags & SG_LISTS_SORTED,
+                      list_flags & SG_LISTS_RADIUS, w.parent, w.asym_nodes, w.counters);
     else
       bfs_hook_min_kernel<<<grid, 256, 0, stream>>>(bq_idxs, start_len, n, list_flags & SG_LISTS_SORTED,
                                                    list_flags & SG_LISTS_RADIUS, w.parent);
     bfs_compress_kernel<<<grid, 256, 0, stream>>>(n, w.parent);
   }
-  bfs_union_kernel<0><<<grid_for(n, 4, 256 * 16), 256, 0, stream>>>(bq_idxs, start_len, n,
-                                                                  list_flags & SG_LISTS_SORTED,
-                                                                  list_flags & SG_LISTS_RADIUS,
-                                                                  w.parent, w.asym_nodes, w.counters);
+  launch_union<0>(lanes_union, stream, bq_idxs, start_len, n, list_flags & SG_LISTS_SORTED,
+                  list_flags & SG_LISTS_RADIUS, w.parent, w.asym_nodes, w.counters);
   bfs_flatten_kernel<<<grid, 256, 0, stream>>>(n, w.parent, w.lab);
   bfs_store_root_kernel<<<grid, 256, 0, stream>>>(n, w.lab, w.parent);  // parent := root_of
 
@@ -1943,8 +2029,7 @@ int sg_bfs_cluster_label(const int32_t *bq_idxs, const int32_t *start_len, int n
       const int n_asym = host_counters[0];
       while (true) {
         hipMemsetAsync(w.counters + 1, 0, 4, stream);
-        bfs_propagate_kernel<<<grid_for(n_asym, 4, 256 * 16), 256, 0, stream>>>(
-            bq_idxs, start_len, w.asym_nodes, n_asym, w.parent, w.lab, w.counters);
+        launch_propagate(lanes, stream, bq_idxs, start_len, w.asym_nodes, n_asym, w.parent, w.lab, w.counters);
         host_counters[8] = 0;
         hipMemcpyAsync(host_counters + 8, w.counters + 1, 4, hipMemcpyDeviceToHost, stream);
         if (hipStreamSynchronize(stream) != hipSuccess) return check_launch("bfs propagate");
@@ -2004,8 +2089,7 @@ int sg_bfs_cluster_emit(const int32_t *bq_idxs, const int32_t *start_len, int n,
   bfs_seed_kernel<<<(n + 255) / 256, 256, 0, stream>>>(n, w.label, w.size, w.cid, w.coff,
                                                        seg_of_point, seg_thr, w.seeds,
                                                        cluster_offsets);
-  bfs_edge_rec_kernel<<<grid_for(n, 4, 256 * 16), 256, 0, stream>>>(bq_idxs, w.label, w.cid, w.seeds, n,
-                                                                     n_cluster, w.erec);
+  launch_edge_rec(grouping_lanes_for(n_edges, n), stream, bq_idxs, w.label, w.cid, w.seeds, n, n_cluster, w.erec);
   static const bool want_stats = getenv("SG_BFS_STATS") != nullptr;     // developer tool
   int32_t *stats = nullptr;
   if (want_stats) {

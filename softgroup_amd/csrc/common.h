@@ -104,6 +104,57 @@ __device__ __forceinline__ int wave_max(int v) {
   return v;
 }
 
+// ---- lane groups: G consecutive lanes (8, 16, 32 or 64) work on one node, 64 / G nodes per wave in
+// lock-step.  For neighbour lists of a handful of entries a whole wave per node leaves 60 lanes idle and
+// the kernel's length is (nodes per wave) x (latency of the node's dependent loads); narrow groups walk
+// several nodes' chains at once.  Control flow stays wave-uniform (loops run to the longest group's trip
+// count, per-group predicates mask the work), so the same EXEC-full contract as above holds.
+template <int G>
+__device__ __forceinline__ int group_lane() { return static_cast<int>(threadIdx.x) & (G - 1); }
+template <int G>
+__device__ __forceinline__ uint64_t group_mask() { return G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull); }
+// the wave ballot's bits of this lane's group, shifted down to bit 0
+template <int G>
+__device__ __forceinline__ uint64_t group_ballot(bool p) {
+  const uint64_t b = __ballot(p);
+  if (G == 64) return b;
+  return (b >> (lane_id() & ~(G - 1))) & group_mask<G>();
+}
+template <int G>
+__device__ __forceinline__ bool group_any(bool p) { return group_ballot<G>(p) != 0ull; }
+// exclusive prefix count of the group's set bits below this lane (m = group_ballot)
+template <int G>
+__device__ __forceinline__ int group_mask_prefix(uint64_t m) {
+  if (G == 64) return mask_prefix(m);
+  return __popcll(m & ((1ull << group_lane<G>()) - 1ull));
+}
+// inclusive scan inside every group: wave_incl_scan without the steps that cross a group's boundary
+// (row_shr stays inside a row of 16 lanes; an 8-lane group drops what its upper half would take over)
+template <int G>
+__device__ __forceinline__ int group_incl_scan(int v) {
+  static_assert(G == 8 || G == 16 || G == 32 || G == 64, "lane groups are 8, 16, 32 or 64 lanes");
+  if (G == 8) {
+    const int gl = group_lane<8>();
+    int t = dpp_or_zero<0x111>(v);
+    v += gl >= 1 ? t : 0;
+    t = dpp_or_zero<0x112>(v);
+    v += gl >= 2 ? t : 0;
+    t = dpp_or_zero<0x114>(v);
+    v += gl >= 4 ? t : 0;
+    return v;
+  }
+  v += dpp_or_zero<0x111>(v);
+  v += dpp_or_zero<0x112>(v);
+  v += dpp_or_zero<0x114>(v);
+  v += dpp_or_zero<0x118>(v);
+  if (G >= 32) v += dpp_or_zero<0x142, 0xa>(v);
+  if (G == 64) v += dpp_or_zero<0x143, 0xc>(v);
+  return v;
+}
+// lanes per node for a mean list length (host side): narrow groups only where lists are short
+int grouping_lanes_for(int64_t n_edges, int n);      // bfs.hip: 8 or 64, or what sg_grouping_set_lanes forces
+int grouping_lanes_forced();                         // 0 = automatic
+
 // Several buffers filled by ONE launch (each hipMemsetAsync is a graph node of its own: ~5 us of GPU
 // time and a launch gap; an index build used to issue ten of them).  Regions are 4-byte aligned, sizes
 // multiples of 4; `byte` is replicated like memset's value.
