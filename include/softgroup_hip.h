@@ -1005,6 +1005,31 @@ int sg_inst_scan_update(const int64_t *gts, int64_t n_points, const int32_t *run
                         uint32_t *ex_meta, int64_t ex_cap, int32_t *seg_stats, int64_t *totals, int32_t *flags,
                         void *ws, size_t ws_bytes, sg_stream_t stream);
 
+/* S3DIS coverage / precision / recall of the scan that the last sg_inst_scan_update left in ws (same sizing
+ * arguments, same layout; enqueue it right behind that call, on the same stream).  The reference has no code
+ * for these; the definitions, per scan and evaluated label l:
+ *   GT instances of l: every row of the scan's GT table with that label, ascending id, all sizes.
+ *   participating predictions: label >= 0, pred_vert >= min_region and pred_conf >= score_thr.
+ *   ov_gt(g)   = max IoU over the participating predictions of l (0.0 without any); ov_pred(p) = max IoU over
+ *                the GT instances of l (0.0 without any); IoU = inter / (gt_vert + pred_vert - inter) in double,
+ *                as the pair records hold it (same label, inter > 0).
+ *   cov  = (sum_g ov_gt(g)) / n_gt,  wcov = (sum_g ov_gt(g) * vert(g)) / sum_g vert(g), both only when n_gt > 0
+ *          (the scan is then a "room" of l); gt_hit = GTs with ov_gt >= iou_thr; a participating prediction is a
+ *          tp when ov_pred >= iou_thr, else an fp.
+ * Reads from ws: info (n_gt, pairs), gt_label, gt_vert, gt_pair_off, pred_pair_off, the pred and iou columns of
+ * the pairs by GT and the iou column of the pairs by prediction.  One workgroup per label: the maxima in
+ * parallel, then one lane sums over ascending GT id with a rounded multiply and rounded adds (no fused
+ * multiply-add) and adds to cov_sums (device double [2][n_labels]: cov, wcov) and tallies (device int64
+ * [5][n_labels]: rooms, n_gt, gt_hit, tp, fp), both zero at the start of an evaluation.  No floating-point
+ * atomics: bitwise repeatable, and equal to the host evaluator's sums.  A scan behind a non-zero *flags adds
+ * nothing (that evaluation is redone or handed to the host); table entries are clamped to gt_cap, n_pred and
+ * the pair capacity before anything is indexed. */
+int sg_inst_scan_coverage(int64_t n_points, int n_pred, int64_t run_slots, int n_classes, int gt_cap, int n_thr,
+                          int n_labels, const int32_t *pred_label, const int32_t *pred_vert,
+                          const double *pred_conf, int64_t min_region, double iou_thr, double score_thr,
+                          double *cov_sums, int64_t *tallies, const int32_t *flags, void *ws, size_t ws_bytes,
+                          sg_stream_t stream);
+
 /* The curves (evaluate_matches :146-199): the examples sorted by (segment, score), cumulative true count,
  * np.unique's boundaries, precision / recall in double, AP summed in a fixed order -> ap, rc [n_seg]
  * (0.0 for a segment with GT only, NaN without GT).  ws: sg_inst_curves_workspace_bytes bytes. */

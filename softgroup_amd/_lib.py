@@ -131,6 +131,8 @@ SIGNATURES = {
     'sg_inst_scan_workspace_bytes': (_sz, [_i64, _i, _i64, _i, _i, _i, _i, _vp]),
     'sg_inst_scan_update': (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i, _i,
                                  _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_inst_scan_coverage': (_i, [_i64, _i, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _d, _d, _vp, _vp, _vp, _vp,
+                                   _sz, _vp]),
     'sg_inst_curves_workspace_bytes': (_sz, [_i64, _i]),
     'sg_inst_curves': (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sg_det_boxes_runs': (_i, [_vp, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -13,6 +13,8 @@
 //                       then emit at scanned offsets) and appends (score key, segment, true flag)
 //                       examples to the evaluation's accumulator.  The walk is sequential only inside one
 //                       (scan, label, threshold): the reference's `visited` keys carry the scan id.
+//   sg_inst_scan_coverage  (opt-in) the S3DIS columns from the same pair records: per label the best IoU of
+//                       every GT and of every prediction, coverage sums in ascending GT order, tp / fp tallies
 //   sg_inst_curves      examples ordered by (segment, score key) with three stable LSD radix sorts, then a
 //                       workgroup per (label, threshold): cumulative true count, unique score boundaries,
 //                       precision / recall in double, AP summed in a fixed order.
@@ -501,6 +503,98 @@ __global__ void __launch_bounds__(kIeBlock) ie_match_kernel(IeScan t, IePreds pr
   if (threadIdx.x == 0) acc.totals[0] = base + carry;
 }
 
+// ---- 3b. coverage, precision and recall of the scan (S3DIS tables; no reference code, softgroup_hip.h
+// states the definitions) -------------------------------------------------------------------------------
+struct IeCov {
+  double iou_thr, score_thr;
+  double *sums;            // [2][n_labels]: cov, wcov summed over the rooms
+  int64_t *tallies;        // [5][n_labels]: rooms, n_gt, gt_hit, tp, fp
+  const int32_t *flags;
+  int n_labels;
+};
+
+// one workgroup per label.  The maxima are order-free: a thread per prediction, then a thread per GT row,
+// kIeBlock rows at a time; thread 0 adds each batch in ascending row (= id) order, so the sums are the
+// host's, bit for bit.
+__global__ void __launch_bounds__(kIeBlock) ie_coverage_kernel(IeScan t, IePreds pr, IeCov c) {
+  __shared__ double ov_s[kIeBlock];
+  __shared__ int32_t vert_s[kIeBlock];
+  __shared__ uint8_t on_s[kIeBlock];
+  __shared__ int cnt_s[2];
+  if (*c.flags) return;                                  // (uniform) this evaluation is redone or the host's
+  const int label = blockIdx.x, tid = threadIdx.x;
+  const int n_pred = t.n_pred;
+  int n_gt = t.info[0], n_pairs = t.info[2];
+  n_gt = n_gt < 0 ? 0 : (n_gt > t.gt_cap ? t.gt_cap : n_gt);
+  n_pairs = n_pairs < 0 ? 0 : (n_pairs > t.pair_cap ? static_cast<int>(t.pair_cap) : n_pairs);
+  if (tid < 2) cnt_s[tid] = 0;
+  __syncthreads();
+  int tp = 0, fp = 0;
+  for (int p = tid; p < n_pred; p += kIeBlock) {
+    if (!ie_kept(pr, p) || pr.label[p] != label || !(pr.conf[p] >= c.score_thr)) continue;
+    int q0 = t.pred_pair_off[p], q1 = t.pred_pair_off[p + 1];
+    if (q0 < 0) q0 = 0;
+    if (q1 > n_pairs) q1 = n_pairs;
+    double ov = 0.0;
+    for (int q = q0; q < q1; ++q) {
+      const double v = t.pb_iou[q];
+      if (v > ov) ov = v;
+    }
+    if (ov >= c.iou_thr) ++tp;
+    else ++fp;
+  }
+  if (tp) atomicAdd(&cnt_s[0], tp);
+  if (fp) atomicAdd(&cnt_s[1], fp);
+  double sum = 0.0, wsum = 0.0;                          // thread 0's
+  int64_t vsum = 0, n = 0, hit = 0;
+  for (int c0 = 0; c0 < n_gt; c0 += kIeBlock) {
+    const int g = c0 + tid;
+    const bool on = g < n_gt && t.gt_label[g] == label;
+    double ov = 0.0;
+    if (on) {
+      int q0 = t.gt_pair_off[g], q1 = t.gt_pair_off[g + 1];
+      if (q0 < 0) q0 = 0;
+      if (q1 > n_pairs) q1 = n_pairs;
+      for (int q = q0; q < q1; ++q) {
+        const int p = t.pa_pred[q];
+        if (p < 0 || p >= n_pred || !(pr.conf[p] >= c.score_thr)) continue;
+        const double v = t.pa_iou[q];
+        if (v > ov) ov = v;
+      }
+    }
+    ov_s[tid] = ov;
+    vert_s[tid] = on ? t.gt_vert[g] : 0;
+    on_s[tid] = on ? 1 : 0;
+    __syncthreads();
+    if (tid == 0) {
+      const int m = n_gt - c0 < kIeBlock ? n_gt - c0 : kIeBlock;
+      for (int i = 0; i < m; ++i) {
+        if (!on_s[i]) continue;
+        sum = __dadd_rn(sum, ov_s[i]);
+        wsum = __dadd_rn(wsum, __dmul_rn(ov_s[i], static_cast<double>(vert_s[i])));
+        vsum += vert_s[i];
+        ++n;
+        hit += ov_s[i] >= c.iou_thr ? 1 : 0;
+      }
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  if (tid == 0) {
+    // scans follow each other on the stream and a label is one workgroup's: plain updates
+    const int L = c.n_labels;
+    if (n > 0) {
+      c.tallies[label] += 1;
+      c.tallies[L + label] += n;
+      c.tallies[2 * L + label] += hit;
+      c.sums[label] = __dadd_rn(c.sums[label], __ddiv_rn(sum, static_cast<double>(n)));
+      c.sums[L + label] = __dadd_rn(c.sums[L + label], __ddiv_rn(wsum, static_cast<double>(vsum)));
+    }
+    c.tallies[3 * L + label] += cnt_s[0];
+    c.tallies[4 * L + label] += cnt_s[1];
+  }
+}
+
 // ---- 4. curves (:146-199) -------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kIeBlock) ie_split_kernel(const uint64_t *__restrict__ key, int64_t n,
                                                             uint32_t *__restrict__ lo, int32_t *__restrict__ idx) {
@@ -727,6 +821,26 @@ int sg_inst_scan_update(const int64_t *gts, int64_t n_points, const int32_t *run
   IeAcc acc{ex_key, ex_meta, ex_cap, seg_stats, totals, flags};
   ie_match_kernel<<<1, kIeBlock, 0, stream>>>(t, pr, thr, n_labels, acc);
   return check_launch("sg_inst_scan_update");
+}
+
+int sg_inst_scan_coverage(int64_t n_points, int n_pred, int64_t run_slots, int n_classes, int gt_cap, int n_thr,
+                          int n_labels, const int32_t *pred_label, const int32_t *pred_vert,
+                          const double *pred_conf, int64_t min_region, double iou_thr, double score_thr,
+                          double *cov_sums, int64_t *tallies, const int32_t *flags, void *ws, size_t ws_bytes,
+                          sg_stream_t stream_) {
+  SG_REQUIRE(ie_scan_args_ok(n_points, n_pred, run_slots, n_classes, gt_cap, n_thr, n_labels) && cov_sums &&
+                 tallies && flags && ws && (n_pred == 0 || (pred_label && pred_vert && pred_conf)) &&
+                 min_region >= 1 && iou_thr == iou_thr && score_thr == score_thr,
+             "sg_inst_scan_coverage: bad arguments");
+  IeScan t;
+  if (!ie_carve(ws, ws_bytes, n_pred, run_slots, n_classes, gt_cap, n_thr, n_labels, &t, nullptr, nullptr)) {
+    set_error("sg_inst_scan_coverage: workspace too small");
+    return SG_ERR_WORKSPACE;
+  }
+  IePreds pr{pred_label, pred_vert, pred_conf, min_region};
+  IeCov c{iou_thr, score_thr, cov_sums, tallies, flags, n_labels};
+  ie_coverage_kernel<<<n_labels, kIeBlock, 0, as_stream(stream_)>>>(t, pr, c);
+  return check_launch("sg_inst_scan_coverage");
 }
 
 size_t sg_inst_curves_workspace_bytes(int64_t n_examples, int n_seg) {

@@ -41,8 +41,31 @@ is the host's.  ``last_backend`` / ``last_fallback`` say what ran: duplicate sca
 whole evaluation to the host path; an accumulator that proves too small is detected by the kernels
 (nothing is truncated silently) and the evaluation is redone with more room from the inputs, which are
 kept by reference until ``compute``; malformed RLE text raises ValueError.
+
+``coverage=True`` (or ``dict(iou_thr=0.5, score_thr=0.0)``) adds the columns of the S3DIS tables (ASIS,
+PointGroup, HAIS, SoftGroup): mean coverage, size-weighted coverage, and precision / recall at one IoU
+threshold.  The reference has no code for them; per scan and evaluated label l they are defined as
+
+  GT instances         the evaluated ids of l, ascending, all sizes
+  participating preds  those that take part above (valid label, >= min region size) with conf >= score_thr
+  ov_gt(g), ov_pred(p) the best IoU over the participating predictions / the GT instances of l, 0.0 without any
+  cov, wcov            (sum_g ov_gt(g)) / n_gt and (sum_g ov_gt(g) * vert(g)) / sum_g vert(g), when n_gt > 0
+                       (the scan is then a room of l)
+  tp / fp              a participating prediction with ov_pred >= iou_thr / below it
+  gt_hit               the GT instances with ov_gt >= iou_thr
+
+and over the scans ``cov[l] = sum of cov / rooms[l]`` (the ASIS protocol: mean per room, then over rooms),
+likewise wcov, ``prec[l] = tp / (tp + fp)``, ``rec[l] = gt_hit / n_gt`` (counted on the GT side: with
+duplicate predictions the prediction-side count can exceed n_gt), NaN for a zero denominator, and the
+``all_*`` figures the nanmean over the labels.  The sums run over ascending GT id and scan after scan, with
+a rounded multiply and rounded adds, on the host and in ``sg_inst_scan_coverage`` alike, so both backends
+give the same bits.  Without ``coverage`` nothing of this runs and ``avgs`` is what it always was.
 """
+import warnings
+
 import numpy as np
+
+_COV_TALLIES = ('rooms', 'n_gt', 'gt_hit', 'tp', 'fp')
 
 
 def _runs_of(pred_mask, n_points):
@@ -90,6 +113,7 @@ class _DeviceAccumulator(object):
         self.n_seg = self.n_labels * self.n_thr
         self.thr = np.ascontiguousarray(ev.ious, np.float64)       # the host's float64 values, passed down
         self.min_region = int(ev.min_region_sizes[0])
+        self.coverage = ev.coverage
         cap = ev.device_capacity or {}
         self.ex_cap = int(cap.get('examples', 1 << 20))
         self.gt_cap = int(cap.get('gt', 256))
@@ -104,6 +128,8 @@ class _DeviceAccumulator(object):
         self.ex_meta = torch.empty(max(self.ex_cap, 1), dtype=torch.int32, device=self.dev)
         self.seg_stats = torch.zeros(4 * self.n_seg, dtype=torch.int32, device=self.dev)
         self.meta = torch.zeros(4, dtype=torch.int64, device=self.dev)   # [0] examples, [2] flag word (int32)
+        if self.coverage:                                      # doubles [2][n_labels], then int64 [5][n_labels]
+            self.cov = torch.zeros(7 * self.n_labels, dtype=torch.int64, device=self.dev)
         self.stream = None
 
     def _flags_ptr(self):
@@ -236,6 +262,12 @@ class _DeviceAccumulator(object):
             self.n_labels, self.n_classes, self.min_region, self.thr.ctypes.data, self.n_thr, self.gt_cap,
             self.ex_key.data_ptr(), self.ex_meta.data_ptr(), self.ex_cap, self.seg_stats.data_ptr(),
             self.meta.data_ptr(), self._flags_ptr(), ws.data_ptr(), ws_bytes, st), 'sg_inst_scan_update')
+        if self.coverage:                                      # over the scan's tables, before ws can be reused
+            L.check(lib.sg_inst_scan_coverage(
+                n_points, n_pred, run_slots, self.n_classes, self.gt_cap, self.n_thr, self.n_labels, p_label, p_vert,
+                p_conf, self.min_region, self.coverage['iou_thr'], self.coverage['score_thr'], self.cov.data_ptr(),
+                self.cov.data_ptr() + 16 * self.n_labels, self._flags_ptr(), ws.data_ptr(), ws_bytes, st),
+                'sg_inst_scan_coverage')
         # (stage-level tests look at the scan's tables)
         self._last = dict(ws=ws, blob=blob, runs=runs, gts=d_gts, n_points=n_points, n_pred=n_pred,
                           run_slots=run_slots, vert=blob[offs[3]:offs[3] + 4 * n_pred].view(torch.int32))
@@ -281,6 +313,10 @@ class _DeviceAccumulator(object):
                                    self.n_seg, out.data_ptr(), out.data_ptr() + 8 * self.n_seg, self._flags_ptr(),
                                    ws.data_ptr(), ws_bytes, L.stream()), 'sg_inst_curves')
         res = out.cpu().numpy()
+        if self.coverage:
+            cov = self.cov.cpu().numpy()
+            self.cov_result = (cov[:2 * self.n_labels].view(np.float64).reshape(2, self.n_labels).copy(),
+                               cov[2 * self.n_labels:].reshape(5, self.n_labels).copy())
         if int(self.meta.cpu()[2]) & _INST_NO_EXAMPLES:
             self.fallback = 'a label with GT and predictions but no example (the reference raises IndexError)'
             return None
@@ -291,7 +327,7 @@ class _DeviceAccumulator(object):
 class ScanNetEval(object):
 
     def __init__(self, class_labels, min_npoint=None, iou_type=None, use_label=True, device=None,
-                 backend=None):
+                 backend=None, coverage=None):
         self.valid_class_labels = class_labels
         self.valid_class_ids = np.arange(len(class_labels)) + 1
         self.id2label = {int(i): n for i, n in zip(self.valid_class_ids, class_labels)}
@@ -309,6 +345,16 @@ class ScanNetEval(object):
         self.last_fallback = None  # why a 'device' evaluation was handed to the host path, or None
         # test hook: initial capacities of the device accumulator, dict(examples=..., gt=...)
         self.device_capacity = None
+        # None, or dict(iou_thr, score_thr): mCov / mWCov / mPrec / mRec next to the AP figures
+        self.coverage = None
+        if coverage:
+            given = {} if coverage is True else dict(coverage)
+            unknown = sorted(set(given) - {'iou_thr', 'score_thr'})
+            if unknown:
+                raise ValueError(f'coverage takes iou_thr and score_thr, not {unknown}')
+            self.coverage = dict(iou_thr=float(given.get('iou_thr', 0.5)), score_thr=float(given.get('score_thr', 0.0)))
+            if np.isnan(self.coverage['iou_thr']) or np.isnan(self.coverage['score_thr']):
+                raise ValueError('coverage: iou_thr and score_thr must not be NaN')
 
     # ------------------------------------------------------------------ association (per scan)
     def _count_matrix(self, starts, lens, run_pred, n_pred, gt_slot, n_slots):
@@ -498,6 +544,54 @@ class ScanNetEval(object):
                 rc[0, li, oi] = rc_cur
         return ap, rc
 
+    # ------------------------------------------------------------------ coverage, precision, recall
+    def coverage_of_matches(self, matches):
+        """-> (sums float64 [2][n_labels]: cov and wcov summed over the rooms, tallies int64 [5][n_labels]:
+        rooms, n_gt, gt_hit, tp, fp) over the scans of `matches` in their order; plain float64 arithmetic in
+        the order the module text fixes"""
+        iou_thr, score_thr = self.coverage['iou_thr'], self.coverage['score_thr']
+        n_lab = len(self.eval_class_labels)
+        sums, tallies = np.zeros((2, n_lab), np.float64), np.zeros((5, n_lab), np.int64)
+        for m in matches:
+            for li, name in enumerate(self.eval_class_labels):
+                gts = matches[m]['gt'][name]                   # ascending instance id
+                if gts:
+                    s, w = np.float64(0.0), np.float64(0.0)
+                    vert = hit = 0
+                    for gt in gts:
+                        ov = 0.0
+                        for pred in gt['matched_pred']:
+                            if float(pred['confidence']) >= score_thr and pred['iou'] > ov:
+                                ov = pred['iou']
+                        s = s + np.float64(ov)
+                        w = w + np.float64(ov) * np.float64(gt['vert_count'])
+                        vert += gt['vert_count']
+                        hit += 1 if ov >= iou_thr else 0
+                    tallies[0, li] += 1
+                    tallies[1, li] += len(gts)
+                    tallies[2, li] += hit
+                    sums[0, li] = sums[0, li] + s / np.float64(len(gts))
+                    sums[1, li] = sums[1, li] + w / np.float64(vert)
+                for pred in matches[m]['pred'][name]:
+                    if not float(pred['confidence']) >= score_thr:
+                        continue
+                    ov = max((gt['iou'] for gt in pred['matched_gt']), default=0.0)
+                    tallies[3 if ov >= iou_thr else 4, li] += 1
+        return sums, tallies
+
+    def add_coverage_averages(self, avgs, sums, tallies):
+        rooms, n_gt, hit, tp, fp = (tallies[i] for i in range(5))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            cols = dict(cov=sums[0] / rooms, wcov=sums[1] / rooms, prec=tp / (tp + fp), rec=hit / n_gt)
+        for key, v in cols.items():
+            with warnings.catch_warnings():                    # every label NaN: NaN, quietly
+                warnings.simplefilter('ignore', RuntimeWarning)
+                avgs['all_' + key] = np.nanmean(v)
+            for li, name in enumerate(self.eval_class_labels):
+                avgs['classes'][name][key] = v[li]
+        avgs['coverage_counts'] = {k: tallies[i].astype(np.int64) for i, k in enumerate(_COV_TALLIES)}
+        return avgs
+
     def compute_averages(self, aps, rcs):
         o50 = np.where(np.isclose(self.ious, 0.5))
         o25 = np.where(np.isclose(self.ious, 0.25))
@@ -530,6 +624,8 @@ class ScanNetEval(object):
             gt2pred, pred2gt = self.assign_instances_for_scan(preds, gts)
             matches[f'gt_{i}'] = {'gt': gt2pred, 'pred': pred2gt}
         avgs = self.compute_averages(*self.evaluate_matches(matches))
+        if self.coverage:
+            self.add_coverage_averages(avgs, *self.coverage_of_matches(matches))
         if verbose:
             self.print_results(avgs)
         return avgs
@@ -571,12 +667,17 @@ class ScanNetEval(object):
                     gt2pred, pred2gt = self.assign_instances_for_scan(preds, _host_gts(gts))
                     matches[f'gt_{i}'] = {'gt': gt2pred, 'pred': pred2gt}
                 res = self.evaluate_matches(matches)
+                cov = self.coverage_of_matches(matches) if self.coverage else None
             else:
                 self.last_backend, self.last_fallback = 'device', None
+                cov = self._dev.cov_result if self.coverage else None
         else:
             self.last_backend, self.last_fallback = 'host', None
             res = self.evaluate_matches(self._matches)
+            cov = self.coverage_of_matches(self._matches) if self.coverage else None
         avgs = self.compute_averages(*res)
+        if cov is not None:
+            self.add_coverage_averages(avgs, *cov)
         if verbose:
             self.print_results(avgs)
         return avgs
@@ -597,6 +698,18 @@ class ScanNetEval(object):
         print('{:<15}'.format('average') + ':' + ''.join('{:>8.3f}'.format(avgs[k]) for k in alls))
         print('#' * width)
         print()
+        if 'all_cov' in avgs:
+            cols, keys = ('mCov', 'mWCov', 'mPrec', 'mRec'), ('cov', 'wcov', 'prec', 'rec')
+            print('#' * width)
+            print('{:<15}'.format('what') + ':' + ''.join('{:>8}'.format(c) for c in cols))
+            print('#' * width)
+            for name in self.eval_class_labels:
+                c = avgs['classes'][name]
+                print('{:<15}'.format(name) + ':' + ''.join('{:>8.3f}'.format(c[k]) for k in keys))
+            print('-' * width)
+            print('{:<15}'.format('average') + ':' + ''.join('{:>8.3f}'.format(avgs['all_' + k]) for k in keys))
+            print('#' * width)
+            print()
 
     def write_result_file(self, avgs, filename):
         with open(filename, 'w') as f:

@@ -15,6 +15,11 @@ np.logical_and per same-class (prediction, GT) pair -- is timed as well.  The av
 are compared before anything is reported.
 
     python tools/inst_eval_bench.py [--reps 5] [--write]      (--write: profiles/inst_eval_bench.txt)
+
+--coverage measures what ScanNetEval(coverage=True) (mCov / mWCov / mPrec / mRec) adds instead: on the same two
+sets the device path's three figures with the metrics off, on, and off again (the second "off" shows the noise
+of the run), the host path's wall time off and on, and the four averages of both paths, which must be equal to
+the bit.  It writes profiles/coverage_eval_bench.txt.
 """
 import argparse
 import json
@@ -120,14 +125,56 @@ def same(a, b):
     return (np.isnan(a) and np.isnan(b)) or abs(a - b) <= 1e-12
 
 
+def coverage_main(args, sets):
+    rows = []
+    for kind, n_scans, n_points, n_inst, n_false in sets:
+        made = [make_scan(f'{kind}{s}', 100 + s, n_points, n_inst, n_false) for s in range(n_scans)]
+        pl, gl = [m[0] for m in made], [m[1] for m in made]
+        off, on = ScanNetEval(list(CLASSES)), ScanNetEval(list(CLASSES), coverage=True)
+        host = on.evaluate(pl, gl, verbose=False, backend='host')
+        dev = on.evaluate(pl, gl, verbose=False, backend='device')
+        assert on.last_backend == 'device', on.last_fallback
+        keys = ('all_cov', 'all_wcov', 'all_prec', 'all_rec')
+        assert all(float(host[k]).hex() == float(dev[k]).hex() for k in keys), 'device and host coverage differ'
+        assert all(np.array_equal(v, dev['coverage_counts'][k]) for k, v in host['coverage_counts'].items())
+        assert same({k: v for k, v in dev.items() if k != 'coverage_counts'},
+                    {k: v for k, v in host.items() if k != 'coverage_counts'}), 'device and host averages differ'
+        row = dict(set=kind, scans=n_scans, points=n_points,
+                   preds_per_scan=round(sum(len(p) for p in pl) / n_scans, 1), gt_per_scan=n_inst)
+        row.update({'host_' + k: float(host[k]) for k in keys})
+        row.update({'device_' + k: float(dev[k]) for k in keys})
+        for tag, ev in (('off', off), ('on', on), ('off_again', off)):
+            enq, dms, comp = device_parts(ev, pl, gl, args.reps)
+            row.update({f'update_enqueue_ms_{tag}': round(enq, 3), f'update_device_ms_{tag}': round(dms, 3),
+                        f'compute_ms_{tag}': round(comp, 3)})
+        for tag, ev in (('off', off), ('on', on)):
+            row[f'host_ms_per_scan_{tag}'] = round(median_wall_ms(
+                lambda: ev.evaluate(pl, gl, verbose=False, backend='host'), args.reps) / n_scans, 3)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    path = os.path.join(ROOT, 'profiles', 'coverage_eval_bench.txt')
+    with open(path, 'w') as f:
+        arch = getattr(torch.cuda.get_device_properties(0), 'gcnArchName', '?').split(':')[0]
+        f.write(f'tools/inst_eval_bench.py --coverage --reps {args.reps} on {torch.cuda.get_device_name(0)} ({arch})\n')
+        f.write('medians after one warm-up; ScanNetEval with coverage=None (off, off_again) and coverage=True (on) '
+                'timed in the same run; update figures per scan\n')
+        for row in rows:
+            f.write(json.dumps(row) + '\n')
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ref-scans', type=int, default=2, help='scans the reference association is timed on')
     ap.add_argument('--write', action='store_true', help='write profiles/inst_eval_bench.txt')
+    ap.add_argument('--coverage', action='store_true',
+                    help='cost of coverage=True against coverage=None; writes profiles/coverage_eval_bench.txt')
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), 'inst_eval_bench.py measures the device path: it needs a GPU'
     sets = [('scannet', 32, 150000, 30, 25), ('stpls3d', 8, 600000, 100, 50)]
+    if args.coverage:
+        return coverage_main(args, sets)
     rows = []
     for kind, n_scans, n_points, n_inst, n_false in sets:
         made = [make_scan(f'{kind}{s}', 100 + s, n_points, n_inst, n_false) for s in range(n_scans)]
