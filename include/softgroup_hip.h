@@ -1412,6 +1412,76 @@ int sg_optim_sgd_step(const int64_t *table, int n_tensors, const int64_t *chunks
 int sg_optim_scale_grads(const int64_t *table, int n_tensors, const int64_t *chunks, int64_t n_chunks,
                          const float *coef, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Thinning a cloud and carrying results back to every original point (csrc/resample.hip).  The reference has NO
+ * counterpart on the device: dataset/s3dis/downsample.py draws a random sample on the host and raises for
+ * --voxel-size; nothing there re-expresses a result over the full cloud.  All of it is opt-in.  Arithmetic is
+ * integer and IEEE double, selection uses integer atomics only: two calls on the same input give the same bytes.
+ * Every probe loop is bounded by the table capacity (a power of two >= 2 n), every shell walk by a fixed shell
+ * count, and every index read from memory is range-checked before it is used as an address.
+ *
+ * VOXEL-GRID DOWNSAMPLE.  xyz float32 [n, 3] (device), 0 <= n < 2^31, voxel a finite double > 0.
+ * Cell of a point, per axis: c = floor((double)x / voxel) -- one IEEE double division, not a product with the
+ * reciprocal.  A point is INVALID when a coordinate is not finite or |c| >= 2^31: any invalid point sets bit 0 of
+ * meta[1], and then no table is touched, meta[0] = 0 and inverse is all -1 (the flag is decided by a kernel of its
+ * own, before the kernel that inserts).  Representative of an occupied voxel: SG_PICK_FIRST the lowest point index
+ * in it; SG_PICK_CENTER the point with the smallest d2 = (dx*dx + dy*dy) + dz*dz, dx = (double)x - ((double)c + 0.5)
+ * * voxel (double, in that order), the lowest index among equal d2.
+ * sample_ids int32 [>= n]: the representatives in ASCENDING index order (the thinned cloud keeps the point order),
+ * the first meta[0] entries written; inverse int32 [n]: position in sample_ids of the representative of point i's
+ * voxel; meta int32 [2]: [0] = occupied voxels, [1] = flags.  n = 0 writes meta = {0, 0}. */
+#define SG_PICK_FIRST 0
+#define SG_PICK_CENTER 1
+size_t sg_grid_downsample_workspace_bytes(int n);
+int sg_grid_downsample(const float *xyz, int n, double voxel, int pick, int32_t *sample_ids, int32_t *inverse,
+                       int32_t *meta, void *ws, size_t ws_bytes, sg_stream_t stream);
+/* EXACT NEAREST SOURCE POINT.  src float32 [n_src, 3], query float32 [n_query, 3], 1 <= n_src < 2^31,
+ * 0 <= n_query < 2^31.  index[q] = the source j with the smallest d2 = (dx*dx + dy*dy) + dz*dz, dx = (double)qx -
+ * (double)sx (double, in that order), the LOWEST j among equal d2.  With max_dist >= 0 a query whose smallest d2
+ * exceeds max_dist * max_dist gets -1 (max_dist < 0: no limit).  dist2 (double [n_query], may be NULL) = that d2,
+ * +inf where index is -1.  The result equals the brute force over all sources for every query and every cell > 0.
+ *
+ * The grid is a means: sources are counted into a hashed uniform grid of `cell` (cell index floor((double)x / cell),
+ * |index| < 2^30, else the grid is not used at all), a query walks the shells of cells at Chebyshev distance 0, 1, 2
+ * around its own cell and stops after shell R once its best d2 < (R cell)^2 (1 - 2^-18) (after shell 0: once it is
+ * exactly 0) -- the margin covers the rounding of the cell assignment, which moves a cell face by at most 2^-22
+ * cells.  A query not decided after shell 2 (far from every source, in a gap between clusters, outside the grid's
+ * range) goes onto a device work list and a second kernel answers it by a scan of ALL sources, one workgroup per
+ * query, with the same (d2, j) order: such a query costs one scan, never an unbounded walk.
+ * sg_nearest_default_cell (host): about two sources per cell -- with e_k = hi_k - lo_k the extents of the source
+ * bounding box that are > 0 and d their number, cell = (2 * prod e_k / n_src)^(1/d) (1 when d = 0), and at least
+ * max|coordinate| / 2^29 so that the whole box stays inside the grid's range.
+ * meta int32 [2], shared by the two calls: sg_nearest_build zeroes it and sets flag bit 0 of meta[1] for a source
+ * coordinate that is not finite (bit 2: the grid is out of range and unused -- not an error); sg_nearest_query sets
+ * bit 1 for such a query coordinate (its index is -1) and leaves in meta[0] the number of queries the full scan
+ * answered.  With bit 0 set every index is -1 and nothing is scanned: the error costs O(n_query).  grid: >= sg_nearest_grid_bytes(n_src) bytes that sg_nearest_build fills and any number of queries with
+ * the same src, n_src and cell read. */
+double sg_nearest_default_cell(const double *lo, const double *hi, int64_t n_src);
+size_t sg_nearest_grid_bytes(int n_src);
+int sg_nearest_build(const float *src, int n_src, double cell, void *grid, size_t grid_bytes, int32_t *meta,
+                     sg_stream_t stream);
+size_t sg_nearest_query_workspace_bytes(int n_query);
+int sg_nearest_query(const float *src, int n_src, double cell, const void *grid, size_t grid_bytes, const float *query,
+                     int n_query, double max_dist, int32_t *index, double *dist2, int32_t *meta, void *ws,
+                     size_t ws_bytes, sg_stream_t stream);
+/* MASKS THROUGH AN INDEX MAP.  bits uint32 [n_inst, ceil(n_src / 32)] (the bit rows of sg_mask_nms), index int32
+ * [n_out] -> out uint32 [n_inst, ceil(n_out / 32)]: bit i of row k = bit index[i] of source row k, 0 where
+ * index[i] < 0; bits at and beyond n_out are written as 0 and every word of every row is written.  An index >=
+ * n_src is a caller error that reads nothing: it counts as -1 and sets bit 0 of *meta (int32, may be NULL; zeroed
+ * by the call). */
+int sg_mask_bits_gather(const uint32_t *bits, int n_inst, int64_t n_src, const int32_t *index, int64_t n_out,
+                        uint32_t *out, int32_t *meta, sg_stream_t stream);
+/* Bit rows -> runs, in two passes over the same workspace (>= sg_mask_runs_workspace_bytes; 0 = outside the range
+ * n_points < 2^31 and n_inst * ceil(n_points / 2) < 2^31, the calls then return SG_ERR_UNSUPPORTED).  The count pass
+ * writes bounds int64 [n_inst + 1], the exclusive prefix of the runs per row with the total in bounds[n_inst]; the
+ * fill pass writes the first `capacity` runs: starts / ends int32, 0-based, end exclusive, ascending, maximal --
+ * what sg_rle_format_device and sg_mask_bits_from_runs take.  Bits at and beyond n_points are ignored. */
+size_t sg_mask_runs_workspace_bytes(int n_inst, int64_t n_points);
+int sg_mask_runs_count(const uint32_t *bits, int n_inst, int64_t n_points, int64_t *bounds, void *ws, size_t ws_bytes,
+                       sg_stream_t stream);
+int sg_mask_runs_fill(const uint32_t *bits, int n_inst, int64_t n_points, const void *ws, size_t ws_bytes,
+                      int32_t *starts, int32_t *ends, int64_t capacity, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,17 @@ SIGNATURES = {
     'sg_optim_adam_step': (_i, [_vp, _i, _vp, _i64, _d, _d, _d, _d, _d, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     'sg_optim_sgd_step': (_i, [_vp, _i, _vp, _i64, _d, _d, _d, _d, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     'sg_optim_scale_grads': (_i, [_vp, _i, _vp, _i64, _vp, _vp]),
+    'sg_grid_downsample_workspace_bytes': (_sz, [_i]),
+    'sg_grid_downsample': (_i, [_vp, _i, _d, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_nearest_default_cell': (_d, [_vp, _vp, _i64]),
+    'sg_nearest_grid_bytes': (_sz, [_i]),
+    'sg_nearest_build': (_i, [_vp, _i, _d, _vp, _sz, _vp, _vp]),
+    'sg_nearest_query_workspace_bytes': (_sz, [_i]),
+    'sg_nearest_query': (_i, [_vp, _i, _d, _vp, _sz, _vp, _i, _d, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_mask_bits_gather': (_i, [_vp, _i, _i64, _vp, _i64, _vp, _vp, _vp]),
+    'sg_mask_runs_workspace_bytes': (_sz, [_i, _i64]),
+    'sg_mask_runs_count': (_i, [_vp, _i, _i64, _vp, _vp, _sz, _vp]),
+    'sg_mask_runs_fill': (_i, [_vp, _i, _i64, _vp, _sz, _vp, _vp, _i64, _vp]),
 }
 
 

@@ -37,6 +37,7 @@ SOURCES = [
     ('result_io.hip', ['-ffp-contract=off']),
     ('viz_io.hip', ['-ffp-contract=off']),
     ('mask_nms.hip', ['-ffp-contract=off']),
+    ('resample.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('optim.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),

@@ -6,3 +6,5 @@ from .functions import (ball_query, ballquery_batch_p, bfs_cluster, bfs_cluster_
                         voxelization, voxelization_idx)
 from .losses import assign_proposals, instance_losses, point_wise_loss  # noqa: F401
 from .nms import mask_bits_from_runs, mask_nms, mask_nms_numpy  # noqa: F401
+from .resample import (grid_downsample, mask_bits_gather, mask_runs_from_bits,  # noqa: F401
+                       nearest_index)
