@@ -1482,6 +1482,93 @@ int sg_mask_runs_count(const uint32_t *bits, int n_inst, int64_t n_points, int64
 int sg_mask_runs_fill(const uint32_t *bits, int n_inst, int64_t n_points, const void *ws, size_t ws_bytes,
                       int32_t *starts, int32_t *ends, int64_t capacity, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Large clouds: overlapping tiles, one scan per tile at full resolution, instances that straddle a cut joined
+ * again (csrc/stitch.hip).  The reference only cuts blocks offline (dataset/stpls3d/
+ * prepare_data_inst_instance_stpls3d.py) and evaluates every block as a scene of its own.  All of it is opt-in.
+ * Arithmetic is integer and IEEE double, selection uses integer atomics only (compare-and-swap on a key, OR on
+ * bits), orders come from the stable radix sort: two calls on the same input give the same bytes.  Every probe loop
+ * is bounded by the table capacity, every binary search by 32 steps, the component rounds by the instance count;
+ * every index read from memory is range-checked before it is used as an address; no workgroup waits for another.
+ *
+ * TILES.  xyz float32 [n, 3] (device), 0 <= n < 2^29 on the device (the numpy twin: n < 2^31), size a finite double
+ * > 0, 0 <= margin <= size / 2, origin (ox, oy) finite doubles.  Tiles split x and y only.
+ * Core cell of a point, per axis: c = floor(((double)x - o) / size) -- one subtraction, one division.  A point is
+ * INVALID when a coordinate (z included) is not finite or |c| >= 2^30: any invalid point sets bit 0 of meta[1], and
+ * then no table is touched and meta[0] = meta[2] = 0 (the flag is decided by a kernel of its own, before the kernel
+ * that inserts).  The tiles are the cells that hold at least one core point, numbered in ascending (cy, cx) order;
+ * more than 65535 of them set bit 1 of meta[1].
+ * Overlap: with margin == 0 a point belongs to its core tile only.  Otherwise, per axis, lo = o + (double)c * size,
+ * hi = o + (double)(c + 1) * size; the point also belongs on the side c - 1 when (double)x < lo + margin, else on
+ * the side c + 1 when (double)x >= hi - margin (each expression in that order, in double; the "else" only matters
+ * where rounding at margin == size / 2 makes both hold).  The two axes combine: core, x side, y side and the
+ * diagonal, so a point has 1, 2 or 4 candidate cells -- and it joins a neighbouring cell only if that cell is a tile
+ * (fewer tiles, 3 among them, only next to a hole of the tile grid).
+ * The count pass writes meta int32 [4]: [0] = T tiles, [1] = flags, [2] = total = entries of tile_points, and keeps
+ * its state in ws (>= sg_tile_assign_workspace_bytes(n); 0 = n outside the range).  After one read-back of meta the
+ * fill pass (same xyz, n, size, margin, origin and ws; ws2 >= sg_tile_assign_fill_workspace_bytes(total)) writes
+ * tile_cells int32 [T, 2] = (cx, cy), tile_off int64 [T + 1], tile_points int32 [total]: the ASCENDING point indices
+ * of tile t at tile_off[t] .. tile_off[t+1] (a tile keeps the cloud's point order; the order comes from a stable
+ * sort of (tile, point) pairs generated in point order), core_tile int32 [n] and core_pos int32 [n]: the position
+ * of point i in its core tile's list.  The fill pass must not be called when meta[1] != 0. */
+size_t sg_tile_assign_workspace_bytes(int n);
+size_t sg_tile_assign_fill_workspace_bytes(int64_t total);
+int sg_tile_assign_count(const float *xyz, int n, double size, double margin, double ox, double oy, int32_t *meta,
+                         void *ws, size_t ws_bytes, sg_stream_t stream);
+int sg_tile_assign_fill(const float *xyz, int n, double size, double margin, double ox, double oy, int n_tiles,
+                        int64_t total, int32_t *tile_cells, int64_t *tile_off, int32_t *tile_points,
+                        int32_t *core_tile, int32_t *core_pos, const void *ws, size_t ws_bytes, void *ws2,
+                        size_t ws2_bytes, sg_stream_t stream);
+/* SHARED POINTS of two strictly ascending int32 lists a [n_a], b [n_b]: pos_a / pos_b int32 [>= min(n_a, n_b)] = the
+ * positions in each list of the common elements, ascending, the first *count (device int32) entries written.  A
+ * binary search per element of a and an ordered compaction (a prefix sum).  ws >= sg_tile_shared_workspace_bytes. */
+size_t sg_tile_shared_workspace_bytes(int n_a);
+int sg_tile_shared(const int32_t *a, int n_a, const int32_t *b, int n_b, int32_t *pos_a, int32_t *pos_b,
+                   int32_t *count, void *ws, size_t ws_bytes, sg_stream_t stream);
+/* LINKS between the instances of two tiles.  bits_a uint32 [n_a, W], bits_b uint32 [n_b, W], W = ceil(n_bits / 32):
+ * the two tiles' masks restricted to the points S both tiles hold (sg_mask_bits_gather with the shared positions as
+ * the index); bits at and beyond n_bits are ignored on both sides.  ca = population of row i of a = |M(g) n S|,
+ * cb likewise, inter = popcount(a_i & b_j) = |M(g) n M(h)|; den = ca + cb - inter for SG_NMS_IOU, min(ca, cb) for
+ * SG_NMS_MIN.  The pair is LINKED when labels_a[i] == labels_b[j], inter >= min_shared, den > 0 and
+ * (double)inter / (double)den > thr, strictly -- one IEEE division, the rule of sg_mask_nms.  A link sets bit
+ * base_b + j of row base_a + i and bit base_a + i of row base_b + j of adj uint32 [n_total, ceil(n_total / 32)]
+ * (integer OR; the caller zeroes adj once).  adj may be NULL (no decision, labels unused).  Optional outputs:
+ * inter_out int32 [n_a, n_b], cnt_a_out int32 [n_a], cnt_b_out int32 [n_b].
+ * RANGE: n_total <= 16384, n_bits < 2^31, else SG_ERR_UNSUPPORTED. */
+int sg_mask_cross_links(const uint32_t *bits_a, int n_a, const uint32_t *bits_b, int n_b, int64_t n_bits,
+                        const int32_t *labels_a, const int32_t *labels_b, int base_a, int base_b, int n_total,
+                        double thr, int measure, int min_shared, uint32_t *adj, int32_t *inter_out,
+                        int32_t *cnt_a_out, int32_t *cnt_b_out, sg_stream_t stream);
+/* OBJECTS: comp int32 [n_total], comp[g] = the smallest member of g's connected component in the symmetric
+ * adjacency bit matrix (bits at and beyond n_total ignored).  One workgroup, labels in LDS, min-label propagation
+ * with pointer jumping, at most n_total + 1 rounds.  n_total <= 16384, else SG_ERR_UNSUPPORTED. */
+int sg_stitch_components(const uint32_t *adj, int n_total, int32_t *comp, sg_stream_t stream);
+/* SET BITS AS GLOBAL IDS.  bits uint32 [n_inst, ceil(n_bits / 32)] (a tile's rows).  The count pass writes
+ * cnt[k] = population of row k and core_cnt[k] = its set bits p with core[p] != 0 (core uint8 [n_bits], NULL = 0).
+ * The fill pass writes for row k, in bit order from row_off[k] (int64, device): ids = map[p] (map int32 [n_bits],
+ * the tile's point list) and keys = row_key[k] (int32; negative = no object, written as 0xFFFF).  A map value
+ * outside [0, n_points) sets bit 0 of *meta (int32, zeroed by the caller) and the entry becomes (0, 0xFFFF).
+ * Entries at and beyond `capacity` are not written. */
+int sg_mask_bits_ids_count(const uint32_t *bits, int n_inst, int64_t n_bits, const uint8_t *core, int32_t *cnt,
+                           int32_t *core_cnt, sg_stream_t stream);
+int sg_mask_bits_ids_fill(const uint32_t *bits, int n_inst, int64_t n_bits, const int32_t *map, int64_t n_points,
+                          const int64_t *row_off, const int32_t *row_key, int32_t *ids, uint32_t *keys,
+                          int64_t capacity, int32_t *meta, sg_stream_t stream);
+/* UNION of the members' ids per object as maximal runs -- no row over the full cloud exists anywhere: memory is
+ * proportional to total = the sum of the mask populations.  ids int32 [total], keys uint32 [total] (object number;
+ * an entry with key >= n_obj or id outside [0, n_points) belongs to no object).  The pairs are ordered by
+ * (object, id) with two stable radix sorts; equal neighbours inside an object collapse, ids that differ by 1
+ * continue a run.  The count pass writes bounds int64 [n_obj + 1] (exclusive prefix of the runs per object, the
+ * total in bounds[n_obj]) and keeps the sorted pairs in ws; the fill pass writes the first `capacity` runs: starts /
+ * ends int32, 0-based, end exclusive, ascending -- what sg_rle_format_device takes.
+ * RANGE: n_obj <= 16384, total < 2^31, n_points < 2^31; beyond it sg_stitch_union_workspace_bytes returns 0 and
+ * the calls SG_ERR_UNSUPPORTED -- nothing is truncated. */
+size_t sg_stitch_union_workspace_bytes(int64_t total, int n_obj, int64_t n_points);
+int sg_stitch_union_count(const int32_t *ids, const uint32_t *keys, int64_t total, int n_obj, int64_t n_points,
+                          int64_t *bounds, void *ws, size_t ws_bytes, sg_stream_t stream);
+int sg_stitch_union_fill(int64_t total, int n_obj, int64_t n_points, const void *ws, size_t ws_bytes, int32_t *starts,
+                         int32_t *ends, int64_t capacity, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

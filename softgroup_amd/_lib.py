@@ -202,6 +202,19 @@ SIGNATURES = {
     'sg_mask_runs_workspace_bytes': (_sz, [_i, _i64]),
     'sg_mask_runs_count': (_i, [_vp, _i, _i64, _vp, _vp, _sz, _vp]),
     'sg_mask_runs_fill': (_i, [_vp, _i, _i64, _vp, _sz, _vp, _vp, _i64, _vp]),
+    'sg_tile_assign_workspace_bytes': (_sz, [_i]),
+    'sg_tile_assign_fill_workspace_bytes': (_sz, [_i64]),
+    'sg_tile_assign_count': (_i, [_vp, _i, _d, _d, _d, _d, _vp, _vp, _sz, _vp]),
+    'sg_tile_assign_fill': (_i, [_vp, _i, _d, _d, _d, _d, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'sg_tile_shared_workspace_bytes': (_sz, [_i]),
+    'sg_tile_shared': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_mask_cross_links': (_i, [_vp, _i, _vp, _i, _i64, _vp, _vp, _i, _i, _i, _d, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'sg_stitch_components': (_i, [_vp, _i, _vp, _vp]),
+    'sg_mask_bits_ids_count': (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp]),
+    'sg_mask_bits_ids_fill': (_i, [_vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    'sg_stitch_union_workspace_bytes': (_sz, [_i64, _i, _i64]),
+    'sg_stitch_union_count': (_i, [_vp, _vp, _i64, _i, _i64, _vp, _vp, _sz, _vp]),
+    'sg_stitch_union_fill': (_i, [_i64, _i, _i64, _vp, _sz, _vp, _vp, _i64, _vp]),
 }
 
 

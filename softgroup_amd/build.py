@@ -38,6 +38,7 @@ SOURCES = [
     ('viz_io.hip', ['-ffp-contract=off']),
     ('mask_nms.hip', ['-ffp-contract=off']),
     ('resample.hip', ['-ffp-contract=off']),
+    ('stitch.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('optim.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),

@@ -410,3 +410,4 @@ def prefetch_device(batches, collate=None, depth=1, device='cuda', workers=1):
 from .train import TrainTransform, collate_train_device  # noqa: E402,F401
 from .test import TestTransform, collate_x4_test_device  # noqa: E402,F401
 from .downsample import apply_sample, random_downsample, voxel_downsample  # noqa: E402,F401
+from .tiles import TileSet, tile_cloud  # noqa: E402,F401
