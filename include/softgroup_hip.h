@@ -697,6 +697,63 @@ int sg_mask_bits_from_runs(const int32_t *starts, const int32_t *ends, const int
                            int n_inst, int64_t n_points, uint32_t *bits, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Masks cut into their spatially connected components (csrc/mask_split.hip).  The reference has NO counterpart:
+ * nothing in its get_instances looks at geometry, so a mask may be an object plus stray points elsewhere, or two
+ * objects of one class welded into one proposal.  This stage is new and opt-in (test_cfg.split); nothing calls it
+ * unless asked.  softgroup_amd.ops.split.mask_components_numpy is the definition, the kernels equal it.
+ *
+ * INPUTS: xyz float32 [n_points, 3] (device); bits uint32 [n_inst, ceil(n_points / 32)], the rows of sg_mask_nms
+ * (point i = bit i % 32 of word i / 32, bits at and beyond n_points ignored); radius a finite double > 0 whose
+ * square is finite; min_npoint >= 1; mode SG_SPLIT_ALL ('split') or SG_SPLIT_LARGEST ('largest').
+ * ADJACENCY: inside ONE mask, points p != q are adjacent when, with dx = (double)x_p - (double)x_q (dy, dz
+ * likewise), (dx*dx + dy*dy) + dz*dz <= radius*radius -- inclusive, IEEE double, that association, no
+ * contraction.  Points with equal coordinates are adjacent.  A point of two masks is a node of its own in each:
+ * connectivity never passes from one mask to another.
+ * COMPONENTS: the connected components of that graph; KEY of a component = its smallest point index, SIZE = its
+ * number of points.  SG_SPLIT_ALL: every component with size >= min_npoint is an output.  SG_SPLIT_LARGEST: per
+ * mask only the component of greatest size, the smaller key among equal sizes, and only if its size reaches
+ * min_npoint.  A mask without a surviving component (an empty one included) yields nothing.
+ * OUTPUTS in ascending (source mask, key) order: out_bits uint32 [n_out, ceil(n_points / 32)] (every word written,
+ * bits at and beyond n_points zero), source int32 [n_out] = index of the input mask, npoint int32 [n_out].
+ * INVALID INPUT: a coordinate of a MASK point (points in no mask are never looked at) that is not finite sets
+ * SG_SPLIT_FLAG_NOT_FINITE, one whose cell floor((double)x / radius) reaches 2^31 in magnitude
+ * SG_SPLIT_FLAG_CELL_RANGE; the flag is decided by a kernel of its own before any table is touched, and then
+ * nothing is labelled and meta[0] = 0.
+ * The hashed grid of cells of `radius` is a means: two points within the radius lie at most one cell apart per axis,
+ * or two where the quotient of one of them lies within rounding of a cell face, and the walk covers both -- the
+ * result equals the brute force over all pairs of a mask for every input.
+ *
+ * TWO PASSES over one workspace.  sg_mask_split_count writes meta int32 [4] (device): [0] = n_out, [1] = flags,
+ * [2] = P = mask points in all = sum of the rows' populations (INT32_MAX when more), [3] = components before the
+ * selection (0 with a validity flag).  After one read-back of meta, sg_mask_split_fill (same n_inst, n_points and
+ * ws, n_pairs = meta[2]) writes the first `capacity` outputs; it must not be called when meta[1] != 0.
+ * WORKSPACE: memory is proportional to P, which only the device knows: sg_mask_split_workspace_bytes(n_inst,
+ * n_points, n_pairs) is the size for up to n_pairs mask points (100 - 160 bytes each, and 4 per word of bits).  The
+ * count pass first counts P (a prefix over the words) and reads it back -- it synchronises `stream` ONCE -- and
+ * when ws_bytes < sg_mask_split_workspace_bytes(n_inst, n_points, P) it returns SG_ERR_WORKSPACE having written
+ * nothing beyond the prefix: meta[2] holds P, call again with that size.  It needs at least
+ * sg_mask_split_workspace_bytes(n_inst, n_points, 0) to count.
+ * RANGE: n_inst <= 16384, n_out <= 16384, n_points < 2^31, P < 2^31.  sg_mask_split_workspace_bytes returns 0 and
+ * the calls SG_ERR_UNSUPPORTED outside the range that the host can see (n_inst, n_points, n_pairs; P once counted);
+ * more than 16384 outputs set SG_SPLIT_FLAG_TOO_MANY (meta[0] still holds their number, the fill pass then writes
+ * nothing) -- nothing is truncated.
+ * DETERMINISM: integer atomics only (compare-and-swap on a union-find parent with parent[i] <= i, add on sizes,
+ * max on a (size, ~key) word, OR on bits); every order that reaches an output comes from indices: two calls on the
+ * same input give the same bytes.  No thread waits for another; every loop has a bound that does not depend on the
+ * data beyond P, and a bound that is hit sets SG_SPLIT_FLAG_INTERNAL instead of spinning. */
+#define SG_SPLIT_ALL 0
+#define SG_SPLIT_LARGEST 1
+#define SG_SPLIT_FLAG_NOT_FINITE 1
+#define SG_SPLIT_FLAG_CELL_RANGE 2
+#define SG_SPLIT_FLAG_INTERNAL 4
+#define SG_SPLIT_FLAG_TOO_MANY 8
+size_t sg_mask_split_workspace_bytes(int n_inst, int64_t n_points, int64_t n_pairs);
+int sg_mask_split_count(const float *xyz, const uint32_t *bits, int n_inst, int64_t n_points, double radius,
+                        int min_npoint, int mode, int32_t *meta, void *ws, size_t ws_bytes, sg_stream_t stream);
+int sg_mask_split_fill(int n_inst, int64_t n_points, int64_t n_pairs, const void *ws, size_t ws_bytes,
+                       int64_t capacity, uint32_t *out_bits, int32_t *source, int32_t *npoint, sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Native host driver of the grouping head and of the result extraction (csrc/scan_exec.hip): what
  * SoftGroup.forward_grouping + clusters_voxelization (softgroup/model/softgroup.py:411-480,655-709)
  * and get_instances (:537-604) do between the network's dense heads, as one C call each --

@@ -111,6 +111,9 @@ SIGNATURES = {
     'sg_mask_nms_workspace_bytes': (_sz, [_i, _i64]),
     'sg_mask_nms': (_i, [_vp, _i, _i64, _vp, _vp, _d, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sg_mask_bits_from_runs': (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp]),
+    'sg_mask_split_workspace_bytes': (_sz, [_i, _i64, _i64]),
+    'sg_mask_split_count': (_i, [_vp, _vp, _i, _i64, _d, _i, _i, _vp, _vp, _sz, _vp]),
+    'sg_mask_split_fill': (_i, [_i, _i64, _i64, _vp, _sz, _i64, _vp, _vp, _vp, _vp]),
     'sg_scan_grouping': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'sg_scan_grouping_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'sg_scan_instances': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),

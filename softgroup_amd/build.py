@@ -37,6 +37,7 @@ SOURCES = [
     ('result_io.hip', ['-ffp-contract=off']),
     ('viz_io.hip', ['-ffp-contract=off']),
     ('mask_nms.hip', ['-ffp-contract=off']),
+    ('mask_split.hip', ['-ffp-contract=off']),
     ('resample.hip', ['-ffp-contract=off']),
     ('stitch.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),

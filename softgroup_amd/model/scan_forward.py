@@ -338,12 +338,13 @@ class ScanForward:
             out[name] = block[o:o + nb].view(npdt).reshape(shape)
         if want_inst and 'instance' in tasks:
             out['pred_instances'] = self._instances(batch['scan_ids'][0], res, hbuf, N, arena,
-                                                    _cfg(model.test_cfg, 'nms'))
+                                                    _cfg(model.test_cfg, 'nms'), _cfg(model.test_cfg, 'split'),
+                                                    coords_float)
         self.last = res
         return out
 
     @staticmethod
-    def _instances(scan_id, res, hbuf, n_points, arena=None, nms=None):
+    def _instances(scan_id, res, hbuf, n_points, arena=None, nms=None, split=None, coords=None):
         r = res.instances
         n = r.n_kept if res.stage >= 4 else 0
         if n == 0:
@@ -355,6 +356,16 @@ class ScanForward:
         text = str(memoryview(h)[r.off_text:r.off_text + r.text_bytes], 'ascii')
         n_points = int(n_points)
         kept = range(n)
+        if split is not None:     # test_cfg.split: the components of the bit rows in the arena, then NMS on that list
+            from ..ops.nms import nms_params
+            from ..ops.split import split_params
+            from ..util.nms import nms_instances
+            from ..util.split import split_rows_device
+            assert coords is not None and int(coords.shape[0]) == n_points
+            whole = [dict(scan_id=scan_id, label_id=label[k], conf=conf[k]) for k in kept]
+            base = arena.data_ptr() + res.instances_base
+            out = split_rows_device(base + r.bits, n, n_points, coords, whole, *split_params(split), arena.device)
+            return out if nms is None else nms_instances(out, *nms_params(nms), backend='auto')
         if nms is not None:       # test_cfg.nms: sg_mask_nms on the bit rows the scan left in the arena
             from ..ops.nms import nms_keep_rows
             base = arena.data_ptr() + res.instances_base

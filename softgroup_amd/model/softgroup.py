@@ -362,6 +362,7 @@ class SoftGroup(nn.Module):
                 st = _scan_local.copy_stream = torch.cuda.Stream()
             early = to_host_begin(dense_results(), st)
         if want_inst:
+            point_coords = coords_float       # (what the masks index, also under lvl_fusion: test_cfg.split)
             if lvl_fusion:
                 batch_idxs = x.indices[:, 0].int()
                 coords_float = ops.voxelization(coords_float, p2v_map)
@@ -393,19 +394,27 @@ class SoftGroup(nn.Module):
                 # (test_cfg.nms filters pred_instances only: the fusion has its own panoptic_skip_iou and keeps
                 # seeing every instance, so a host fusion takes the unfiltered list first)
                 nms = _cfg(tcfg, 'nms')
+                # (test_cfg.split cuts every mask into its connected components first and NMS then runs on the split
+                # list: the NMS inside get_instances is switched off for that call.  The fusion sees neither.)
+                split = _cfg(tcfg, 'split')
                 host_fusion = 'panoptic' in tasks and not fuse_native
                 pred_instances = self.get_instances(scan_ids[0], inst[0], semantic_scores, inst[1],
                                                     inst[2], inst[3], v2p_map=v2p_map,
                                                     lvl_fusion=lvl_fusion,
                                                     _panoptic_sem=semantic_preds if fuse_native else None,
-                                                    _nms=not host_fusion)
+                                                    _nms=not host_fusion and split is None)
                 fused = None
                 if fuse_native:
                     pred_instances, fused = pred_instances
+                elif host_fusion and (nms is not None or split is not None):
+                    fused = self.panoptic_fusion(semantic_preds.cpu().numpy(), pred_instances)
+                if split is not None:
+                    from ..util.split import apply_split
+                    pred_instances = apply_split(pred_instances, point_coords, split, nms,
+                                                 backend='auto' if inst[1].is_cuda else 'numpy')
                 elif host_fusion and nms is not None:
                     from ..ops.nms import nms_params
                     from ..util.nms import nms_instances
-                    fused = self.panoptic_fusion(semantic_preds.cpu().numpy(), pred_instances)
                     pred_instances = nms_instances(pred_instances, *nms_params(nms),
                                                    backend='auto' if inst[1].is_cuda else 'numpy')
                 if 'instance' in tasks:
@@ -890,7 +899,9 @@ class SoftGroup(nn.Module):
         (mask_score > mask_score_thr) has >= min_npoint points; masks are encoded from sorted
         (proposal, point) pairs -- no dense [nProposal, N] matrix is built.
         With ``test_cfg.nms = dict(thr=, measure=, class_agnostic=)`` (no reference counterpart; absent or None
-        changes nothing) the list is filtered by greedy mask NMS, ``softgroup_amd.ops.mask_nms``'s rules."""
+        changes nothing) the list is filtered by greedy mask NMS, ``softgroup_amd.ops.mask_nms``'s rules.
+        ``test_cfg.split`` (masks cut into connected components, also new) is applied by ``forward_test`` to the
+        finished list, before NMS."""
         if proposals_idx.size(0) == 0:
             return []
         tcfg = self.test_cfg

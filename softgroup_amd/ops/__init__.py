@@ -8,5 +8,6 @@ from .losses import assign_proposals, instance_losses, point_wise_loss  # noqa: 
 from .nms import mask_bits_from_runs, mask_nms, mask_nms_numpy  # noqa: F401
 from .resample import (grid_downsample, mask_bits_gather, mask_runs_from_bits,  # noqa: F401
                        nearest_index)
+from .split import mask_components, mask_components_numpy  # noqa: F401
 from .stitch import (mask_cross_links, stitch_components, stitch_union, tile_assign,  # noqa: F401
                      tile_shared)

@@ -6,6 +6,7 @@ from .results import (load_pred_instances, read_int_lines, read_mask, save_gt_in
 from .visualize import (colors_from_result, get_coords_color, save_visualizations,  # noqa: F401
                         write_ply)  # noqa: F401
 from .nms import nms_instances  # noqa: F401
+from .split import split_instances  # noqa: F401
 from .propagate import propagate_result  # noqa: F401
 from .stitch import stitch_results  # noqa: F401
 from ..optim import build_optimizer, clip_grad_norm_  # noqa: F401,E402
