@@ -754,6 +754,65 @@ int sg_mask_split_fill(int n_inst, int64_t n_points, int64_t n_pairs, const void
                        int64_t capacity, uint32_t *out_bits, int32_t *source, int32_t *npoint, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Masks and semantic labels snapped to an over-segmentation, "superpoints" (csrc/superpoint.hip).  The reference has
+ * NO counterpart; ScanNet ships such a segmentation with every scene (`*.segs.json`) and most pipelines refine their
+ * masks and labels on it.  This stage is new and opt-in (softgroup_amd.util.refine_result); nothing calls it unless
+ * asked.  softgroup_amd.ops.superpoint's numpy twins are the definition, the kernels equal them byte for byte.
+ *
+ * IDS: sp int32 [n_points], the superpoint id of every point: arbitrary (not dense, not ordered), anything in
+ * 0 .. 2^31 - 2; -1 = in no superpoint.  An id below -1 or equal to 2^31 - 1 sets SG_SUPERPOINT_FLAG_ID; a kernel of
+ * its own decides that before anything else runs, and with the flag set nothing but meta is written (meta = [0, flag,
+ * 0, 0]).  No id ever addresses memory: ids are sort keys only.
+ * SEGMENTS: a segment is the set of points with one id, its size their number.  Segments are numbered 0 .. S-1 in
+ * ascending id order; inside a segment the points are in ascending index order.
+ * sg_superpoint_index (once per cloud) writes
+ *   order     int32 [n_points]      the points of segment 0, then of segment 1, ...; the first n_valid entries
+ *   seg_of    int32 [n_points]      the segment of a point, -1 for none (every entry written)
+ *   seg_start int32 [n_points + 1]  segment s = order[seg_start[s] .. seg_start[s+1]); the first S + 1 entries
+ *   meta      int32 [4]             [S, flags, n_valid, largest segment size]
+ * and never synchronises; the caller reads meta back once.
+ *
+ * MASK SNAP.  bits: the rows of sg_mask_nms, uint32 [n_inst, ceil(n_points / 32)], bits at and beyond n_points
+ * ignored.  For mask k and segment s, inter = the points of s in mask k; the segment is TAKEN by the mask when
+ * inter >= 1 and (double)inter / (double)size > thr -- strict, one IEEE double division of the two integers; thr a
+ * double in [0, 1].  Output bit (k, p): a point in no superpoint keeps its input bit; SG_SNAP_SNAP gives
+ * taken(k, seg(p)); SG_SNAP_GROW in | taken (only adds points); SG_SNAP_TRIM in & taken (only removes points).
+ * out_bits uint32 [n_inst, ceil(n_points / 32)]: every word written, bits at and beyond n_points zero, rows in the
+ * input order, nothing dropped; it must not alias bits.  npoint int32 [n_inst]: the populations of the output rows.
+ * order / seg_of / seg_start / n_seg / n_valid: what sg_superpoint_index produced for this cloud.
+ * No synchronisation and no read-back.
+ *
+ * LABEL VOTE.  labels int32 [n_points].  Per segment the points whose label lies in 0 .. n_classes - 1 and differs
+ * from ignore_label are counted per class; every other value is not counted.  The winner is the class with the
+ * greatest count, the lowest class among equal counts; every point of the segment receives it (also the points that
+ * carried an uncounted label).  A segment without a counted label keeps every point's own label, and so do the points
+ * in no superpoint.  out_labels int32 [n_points]; seg_label (may be NULL) int32 [n_seg]: the winner, -1 for none.
+ *
+ * A workgroup walks SG_SUPERPOINT_WALK consecutive positions of `order`; a segment that crosses such a boundary is
+ * summed over several workgroups in a global int32 counter (integer adds: no order reaches an output).
+ * RANGE: n_inst <= 16384, n_points < 2^31, 1 <= n_classes <= 256.  Outside it the _workspace_bytes functions return 0
+ * and the calls SG_ERR_UNSUPPORTED -- nothing is truncated.  Every loop is bounded by sizes the host passed; every
+ * index read from order, seg_of or seg_start is range-checked before it addresses anything, so an index array that
+ * sg_superpoint_index did not write gives wrong bits but never a read or a write outside the buffers.
+ * DETERMINISM: integer adds and ORs only; two calls on the same input give the same bytes. */
+#define SG_SNAP_SNAP 0
+#define SG_SNAP_GROW 1
+#define SG_SNAP_TRIM 2
+#define SG_SUPERPOINT_FLAG_ID 1
+#define SG_SUPERPOINT_WALK 2048
+size_t sg_superpoint_index_workspace_bytes(int64_t n_points);
+int sg_superpoint_index(const int32_t *sp, int64_t n_points, int32_t *order, int32_t *seg_of, int32_t *seg_start,
+                        int32_t *meta, void *ws, size_t ws_bytes, sg_stream_t stream);
+size_t sg_mask_snap_workspace_bytes(int n_inst, int64_t n_points, int64_t n_seg);
+int sg_mask_snap(const uint32_t *bits, int n_inst, int64_t n_points, const int32_t *order, const int32_t *seg_of,
+                 const int32_t *seg_start, int64_t n_seg, int64_t n_valid, double thr, int mode, uint32_t *out_bits,
+                 int32_t *npoint, void *ws, size_t ws_bytes, sg_stream_t stream);
+size_t sg_superpoint_vote_workspace_bytes(int64_t n_points, int64_t n_seg, int n_classes);
+int sg_superpoint_vote(const int32_t *labels, int64_t n_points, const int32_t *order, const int32_t *seg_of,
+                       const int32_t *seg_start, int64_t n_seg, int n_classes, int ignore_label, int32_t *out_labels,
+                       int32_t *seg_label, void *ws, size_t ws_bytes, sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Native host driver of the grouping head and of the result extraction (csrc/scan_exec.hip): what
  * SoftGroup.forward_grouping + clusters_voxelization (softgroup/model/softgroup.py:411-480,655-709)
  * and get_instances (:537-604) do between the network's dense heads, as one C call each --

@@ -114,6 +114,12 @@ SIGNATURES = {
     'sg_mask_split_workspace_bytes': (_sz, [_i, _i64, _i64]),
     'sg_mask_split_count': (_i, [_vp, _vp, _i, _i64, _d, _i, _i, _vp, _vp, _sz, _vp]),
     'sg_mask_split_fill': (_i, [_i, _i64, _i64, _vp, _sz, _i64, _vp, _vp, _vp, _vp]),
+    'sg_superpoint_index_workspace_bytes': (_sz, [_i64]),
+    'sg_superpoint_index': (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_mask_snap_workspace_bytes': (_sz, [_i, _i64, _i64]),
+    'sg_mask_snap': (_i, [_vp, _i, _i64, _vp, _vp, _vp, _i64, _i64, _d, _i, _vp, _vp, _vp, _sz, _vp]),
+    'sg_superpoint_vote_workspace_bytes': (_sz, [_i64, _i64, _i]),
+    'sg_superpoint_vote': (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'sg_scan_grouping': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'sg_scan_grouping_pp': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'sg_scan_instances': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),

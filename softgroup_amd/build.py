@@ -38,6 +38,7 @@ SOURCES = [
     ('viz_io.hip', ['-ffp-contract=off']),
     ('mask_nms.hip', ['-ffp-contract=off']),
     ('mask_split.hip', ['-ffp-contract=off']),
+    ('superpoint.hip', ['-ffp-contract=off']),
     ('resample.hip', ['-ffp-contract=off']),
     ('stitch.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),

@@ -9,5 +9,7 @@ from .nms import mask_bits_from_runs, mask_nms, mask_nms_numpy  # noqa: F401
 from .resample import (grid_downsample, mask_bits_gather, mask_runs_from_bits,  # noqa: F401
                        nearest_index)
 from .split import mask_components, mask_components_numpy  # noqa: F401
+from .superpoint import (SuperpointIndex, mask_snap, mask_snap_numpy, superpoint_index,  # noqa: F401
+                         superpoint_index_numpy, superpoint_vote, superpoint_vote_numpy)
 from .stitch import (mask_cross_links, stitch_components, stitch_union, tile_assign,  # noqa: F401
                      tile_shared)
