@@ -1685,6 +1685,77 @@ int sg_stitch_union_count(const int32_t *ids, const uint32_t *keys, int64_t tota
 int sg_stitch_union_fill(int64_t total, int n_obj, int64_t n_points, const void *ws, size_t ws_bytes, int32_t *starts,
                          int32_t *ends, int64_t capacity, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Superpoints for clouds that ship none (csrc/geometry.hip): the exact k nearest neighbours, normal and curvature
+ * per point, and the connected components of "same smooth surface" links, whose ids sg_superpoint_index accepts as
+ * they are.  The reference has no counterpart.  All of it is opt-in: nothing calls it unless asked.
+ * softgroup_amd.ops.geometry's numpy twins are the definition; sg_knn and sg_grow_segments equal them byte for byte,
+ * sg_point_normals to within the rounding of its eigen-solver.  Arithmetic is integer and IEEE double, selection by
+ * comparisons and integer atomics only: two calls on the same input give the same bytes.  Every index read from
+ * memory is range-checked before it addresses anything; every loop has a bound that does not depend on the data.
+ *
+ * K NEAREST OTHER POINTS.  xyz float32 [n, 3], 0 <= n < 2^31, 1 <= k <= SG_KNN_MAX_K (else SG_ERR_UNSUPPORTED and
+ * sg_knn_workspace_bytes returns 0; nothing is launched).  d2 of two points = (dx*dx + dy*dy) + dz*dz, dx =
+ * (double)x_i - (double)x_j (double, in that order).  Row i of idx int32 [n, k] / d2 double [n, k]: the k points
+ * j != i with the smallest (d2, j) in lexicographic order, in that order -- a point with equal coordinates is a
+ * neighbour at distance 0, ties at the k-th place go to the lower index.  With max_dist >= 0 a point with d2 >
+ * max_dist * max_dist is no neighbour (max_dist < 0: no limit).  Missing entries (n - 1 < k, or beyond max_dist) are
+ * -1 / +inf.  The result equals the brute force for every cell > 0.
+ * SG_KNN_MAX_K is 32: a thread keeps its list in LDS, 12 bytes per entry, and 128 threads x 32 entries = 48 KB is
+ * what stays below the 64 KB a kernel gets by default with three workgroups to a CU; 64 would leave one.
+ * The grid is the one of sg_nearest_build (cell index floor((double)x / cell), |index| < 2^30).  A coordinate that is
+ * not finite sets SG_KNN_FLAG_NOT_FINITE in meta[1], a cell index at or beyond 2^30 SG_KNN_FLAG_CELL_RANGE -- by a
+ * kernel of its own, before any table is touched -- and then NO output row is written at all.  A query walks the
+ * shells of cells at Chebyshev distance 0 .. SG_KNN_MAX_SHELL around its own cell and stops after shell R once it
+ * holds k candidates and the k-th d2 < (R cell)^2 (1 - 2^-18) (after shell 0: once it is exactly 0).  With
+ * max_dist >= 0 and ceil(max_dist / cell * (1 + 2^-20)) <= SG_KNN_MAX_SHELL the walk ends after that many shells
+ * and decides every query.  A query not decided by the walk goes onto a device work list and is answered by a scan
+ * of ALL points, one wave per query, with the same (d2, j) order: it costs one scan, never an unbounded walk.
+ * meta int32 [4]: [0] = queries the full scan answered, [1] = flags, [2], [3] = 0.  n = 0 writes meta only.
+ * sg_knn_default_cell (host): about k / 2 points per cell were the cloud spread evenly over its bounding box --
+ * with e_d = hi_d - lo_d the extents that are > 0 and D their number, cell = (max(k, 2) / 2 * prod e_d / n)^(1/D)
+ * (1 when D = 0), and at least max|coordinate| / 2^29 so that the whole box stays inside the grid's range.  Scanned
+ * clouds are surfaces, several times denser where they have points than that estimate: the k-th neighbour then
+ * lies well inside one cell and the walk ends after shell 1 with a few times k candidates seen. */
+#define SG_KNN_MAX_K 32
+#define SG_KNN_MAX_SHELL 3
+#define SG_KNN_FLAG_NOT_FINITE 1
+#define SG_KNN_FLAG_CELL_RANGE 4
+double sg_knn_default_cell(const double *lo, const double *hi, int64_t n, int k);
+size_t sg_knn_workspace_bytes(int64_t n, int k);
+int sg_knn(const float *xyz, int64_t n, int k, double cell, double max_dist, int32_t *idx, double *d2, int32_t *meta,
+           void *ws, size_t ws_bytes, sg_stream_t stream);
+/* NORMAL AND CURVATURE PER POINT.  nbr int32 [n, k] (1 <= k <= 4096, 0 <= n < 2^31, else SG_ERR_UNSUPPORTED): -1 =
+ * no entry; an index outside -1 .. n - 1 is never dereferenced, counts as -1 and sets SG_GEOMETRY_FLAG_INDEX in
+ * meta[1].  The support of point i is i itself followed by its valid neighbours in list order.  Centroid: the
+ * double sum in that order divided by the count.  Covariance: the six double sums, in that order, of the products
+ * of the centred coordinates (dx*dx, dx*dy, dx*dz, dy*dy, dy*dz, dz*dz; dx = (double)x - mean_x).  With T = (cxx +
+ * cyy) + czz the point HAS NO NORMAL -- normal (0, 0, 0), curvature 0 -- when it has fewer than min_neighbours
+ * valid neighbours or when not 0 < T < inf.  Otherwise the normal is the unit eigenvector of the smallest
+ * eigenvalue l0, its sign such that the component of greatest magnitude is positive (the lowest axis among equal
+ * magnitudes), and curvature = max(l0, 0) / (l0 + l1 + l2); both are rounded to float32 at the end.  The solver:
+ * eight cyclic Jacobi sweeps in double on C / T.  meta int32 [4]: [0] = points without a normal, [1] = flags. */
+#define SG_GEOMETRY_FLAG_INDEX 1
+#define SG_GEOMETRY_FLAG_INTERNAL 2
+int sg_point_normals(const float *xyz, int64_t n, const int32_t *nbr, int k, int min_neighbours, float *normals,
+                     float *curvature, int32_t *meta, sg_stream_t stream);
+/* GROWN SEGMENTS.  nbr int32 [n, k] as above, normals float32 [n, 3], curvature float32 [n] or NULL, nbr_d2 double
+ * [n, k] (required when max_dist >= 0, else unused).  Entry m of point i's list, j = nbr[i][m], is a LINK between i
+ * and j when both have a normal (a component that is not 0), fabs((nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j) >= cos_thr
+ * in double from the float32 normals, with curvature both curvatures <= max_curvature (float32 comparison), and
+ * with max_dist >= 0 nbr_d2[i][m] <= max_dist * max_dist (double).  A segment is a connected component of the
+ * links (an entry in either list links both ways).  Components of at least min_size (>= 1) points are numbered
+ * 0 .. n_seg - 1 in ascending order of their smallest point; sp int32 [n] gets that number.  The other points get
+ * -1, or with absorb = 1 the number of the first entry of their own list (list order) that lies in a numbered
+ * component, else -1 -- one pass that reads only the labels from before the pass.
+ * Lock-free union-find with parent[i] <= i (a find ends after n + 1 steps, a union after 2 n + 2 rounds; a bound
+ * that is hit sets SG_GEOMETRY_FLAG_INTERNAL), sizes by integer atomicAdd at the roots, numbers by a scan over the
+ * roots in index order.  meta int32 [4]: [0] = n_seg, [1] = flags, [2] = components of any size. */
+size_t sg_grow_segments_workspace_bytes(int64_t n);
+int sg_grow_segments(const int32_t *nbr, const double *nbr_d2, int64_t n, int k, const float *normals,
+                     const float *curvature, double cos_thr, float max_curvature, double max_dist, int min_size,
+                     int absorb, int32_t *sp, int32_t *meta, void *ws, size_t ws_bytes, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

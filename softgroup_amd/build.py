@@ -40,6 +40,7 @@ SOURCES = [
     ('mask_split.hip', ['-ffp-contract=off']),
     ('superpoint.hip', ['-ffp-contract=off']),
     ('resample.hip', ['-ffp-contract=off']),
+    ('geometry.hip', ['-ffp-contract=off']),
     ('stitch.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('optim.hip', ['-ffp-contract=off']),

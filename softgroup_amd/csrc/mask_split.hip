@@ -30,6 +30,7 @@
 // memory is range-checked before it addresses anything.
 #include "common.h"
 #include "scan.h"
+#include "union_find.h"
 
 namespace sg {
 
@@ -41,13 +42,6 @@ constexpr double kMsCellLimit = 2147483648.0;             // |cell| < 2^31
 // with g = 2^-40 max(1, |y|) <= 2^-9: three cells, four next to a face.
 constexpr double kMsGuard = 1.0 / 1099511627776.0;
 constexpr int kMsHdrTotal = 0, kMsHdrOut = 1;             // int64 words of the workspace header
-
-__device__ __forceinline__ int32_t ms_load(const int32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void ms_store(int32_t *p, int32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // cell of a point; false when a coordinate is not finite or a cell reaches 2^31 (NaN / inf fail the comparison)
 __device__ __forceinline__ bool ms_cell(const float *__restrict__ p, double radius, int32_t c[3]) {
@@ -280,40 +274,7 @@ __global__ void __launch_bounds__(kMsBlock) ms_scatter_kernel(MsArgs a) {
   }
 }
 
-// ---- union-find --------------------------------------------------------------------------------------------------
-// The root of x, halving the path on the way (a store of a grandparent: any ancestor keeps parent[i] <= i and the
-// component).  -1 after P + 1 steps or on a parent that does not descend.
-__device__ __forceinline__ int32_t ms_find(int32_t *parent, int32_t x, int64_t P) {
-  for (int64_t step = 0; step <= P; ++step) {
-    const int32_t p = ms_load(&parent[x]);
-    if (p == x) return x;
-    if (p < 0 || p > x) return -1;
-    const int32_t g = ms_load(&parent[p]);
-    if (g >= 0 && g < p) ms_store(&parent[x], g);
-    x = p;
-  }
-  return -1;
-}
-
-// false when a bound was hit
-__device__ __forceinline__ bool ms_unite(int32_t *parent, int32_t a, int32_t b, int64_t P) {
-  for (int64_t round = 0; round <= 2 * P + 2; ++round) {
-    a = ms_find(parent, a, P);
-    b = ms_find(parent, b, P);
-    if (a < 0 || b < 0) return false;
-    if (a == b) return true;
-    if (a < b) {
-      const int32_t t = a;
-      a = b, b = t;
-    }
-    const int32_t old = atomicCAS(&parent[a], a, b);             // the larger root under the smaller
-    if (old == a) return true;
-    a = old;                                                     // lost: somebody hooked a first; old < a
-    if (a < 0 || a >= P) return false;
-  }
-  return false;
-}
-
+// ---- union-find (union_find.h) -----------------------------------------------------------------------------------
 // One thread per pair: the pairs of lower id of its mask within the radius.
 __global__ void __launch_bounds__(kMsBlock) ms_edges_kernel(MsArgs a) {
   if (a.meta[1] != 0) return;
@@ -354,7 +315,7 @@ __global__ void __launch_bounds__(kMsBlock) ms_edges_kernel(MsArgs a) {
                   const double dx = px - static_cast<double>(v.x), dy = py - static_cast<double>(v.y),
                                dz = pz - static_cast<double>(v.z);
                   if ((dx * dx + dy * dy) + dz * dz <= a.r2)
-                    fine &= ms_unite(a.w.parent, static_cast<int32_t>(i), j, a.w.P);
+                    fine &= uf_unite(a.w.parent, static_cast<int32_t>(i), j, a.w.P);
                 }
               }
               break;
@@ -371,7 +332,7 @@ __global__ void __launch_bounds__(kMsBlock) ms_flatten_kernel(MsArgs a) {
   if (a.meta[1] != 0) return;
   for (int64_t i = blockIdx.x * static_cast<int64_t>(kMsBlock) + threadIdx.x; i < a.w.P;
        i += static_cast<int64_t>(gridDim.x) * kMsBlock) {
-    const int32_t r = ms_find(a.w.parent, static_cast<int32_t>(i), a.w.P);
+    const int32_t r = uf_find(a.w.parent, static_cast<int32_t>(i), a.w.P);
     a.w.root[i] = r;
     if (r < 0) {
       atomicOr(&a.meta[1], SG_SPLIT_FLAG_INTERNAL);

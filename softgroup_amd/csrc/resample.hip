@@ -11,84 +11,14 @@
 // shell walk after kNnMaxShell shells; every index read from memory is range-checked before it addresses
 // anything; a kernel that touches a table first reads the validity flags the kernel before it left in meta[1].
 //
-// The hash table (both users): open addressing, capacity a power of two >= 2 n.  A slot is claimed by the
-// index of the first point that gets there (atomicCAS on `owner`); a later point compares its cell with the
-// cell of the slot's owner, recomputed from the owner's coordinates -- no key has to become visible inside the
-// kernel that inserts.  Which point owns a slot depends on the order of arrival, nothing that is written out does.
-#include "common.h"
-#include "scan.h"
+// The hash table (both users), its build and the validity kernel live in point_grid.h, which geometry.hip shares.
+#include "point_grid.h"
 
 namespace sg {
 
-constexpr int kRsBlock = 256;
 constexpr int kNnMaxShell = 2;                       // shells 0, 1, 2 of cells, then the full scan
 constexpr double kRsCellLimit = 2147483648.0;        // |cell| < 2^31 (sg_grid_downsample)
-constexpr double kNnCellLimit = 1073741824.0;        // |cell| < 2^30 (the nearest-point grid: room for the shells)
-// A point outside shells 0 .. R differs from the query by more than R cells along one axis.  The cell of a
-// coordinate is floor(fl(x / cell)), monotone in x, so cells are intervals whose ends lie within
-// |c| 2^-52 <= 2^-22 cells of the exact k * cell: its d2 is at least (R cell)^2 (1 - 2^-21).  The walk stops
-// below (R cell)^2 (1 - 2^-18), strictly: nothing outside can be nearer, or as near with a lower index.
-constexpr double kNnStopMargin = 1.0 - 1.0 / 262144.0;
-
-constexpr int kFlagBadSrc = 1, kFlagBadQuery = 2, kFlagNoGrid = 4, kFlagBadIndex = 1;
-
-// cell of a point; false when a coordinate is not finite or a cell reaches `limit` (NaN / inf fail the comparison)
-__device__ __forceinline__ bool cell_of(const float *__restrict__ p, double voxel, double limit, int32_t c[3]) {
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double f = floor(static_cast<double>(p[k]) / voxel);
-    const bool in = fabs(f) < limit;
-    ok &= in;
-    c[k] = in ? static_cast<int32_t>(f) : 0;
-  }
-  return ok;
-}
-
-__device__ __forceinline__ uint64_t cell_hash(int32_t cx, int32_t cy, int32_t cz) {
-  const uint64_t a = (static_cast<uint64_t>(static_cast<uint32_t>(cx)) << 32) | static_cast<uint32_t>(cy);
-  return mix64(a ^ mix64(static_cast<uint64_t>(static_cast<uint32_t>(cz)) + 0x9e3779b97f4a7c15ULL));
-}
-
-// slot of point i's cell, claiming a free one; -1 after `cap` probes or on an owner outside [0, n)
-__device__ __forceinline__ int64_t table_insert(int32_t *__restrict__ owner, int64_t cap, const float *__restrict__ xyz,
-                                               int64_t n, double voxel, double limit, int32_t i, const int32_t c[3]) {
-  uint64_t s = cell_hash(c[0], c[1], c[2]) & static_cast<uint64_t>(cap - 1);
-  for (int64_t probe = 0; probe < cap; ++probe) {
-    const int32_t o = atomicCAS(&owner[s], -1, i);
-    if (o == -1 || o == i) return static_cast<int64_t>(s);
-    if (o < 0 || o >= n) return -1;
-    int32_t oc[3];
-    cell_of(xyz + 3 * static_cast<int64_t>(o), voxel, limit, oc);
-    if (oc[0] == c[0] && oc[1] == c[1] && oc[2] == c[2]) return static_cast<int64_t>(s);
-    s = (s + 1) & static_cast<uint64_t>(cap - 1);
-  }
-  return -1;
-}
-
-inline int64_t table_cap(int64_t n) {
-  int64_t cap = 64;
-  while (cap < 2 * n) cap <<= 1;
-  return cap;
-}
-
-// ---- validity ------------------------------------------------------------------------------------------------
-// bit_finite for a coordinate that is not finite, bit_range for a cell at or beyond `limit`
-__global__ void __launch_bounds__(kRsBlock) rs_validate_kernel(const float *__restrict__ xyz, int64_t n, double voxel,
-                                                              double limit, int bit_finite, int bit_range,
-                                                              int32_t *__restrict__ flags) {
-  int bad = 0;
-  for (int64_t i = blockIdx.x * static_cast<int64_t>(kRsBlock) + threadIdx.x; i < n;
-       i += static_cast<int64_t>(gridDim.x) * kRsBlock) {
-    const float *p = xyz + 3 * i;
-    int32_t c[3];
-    if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])))
-      bad |= bit_finite;
-    else if (!cell_of(p, voxel, limit, c))
-      bad |= bit_range;
-  }
-  if (bad) atomicOr(flags, bad);
-}
+constexpr int kFlagBadIndex = 1;
 
 // ---- voxel-grid downsample -----------------------------------------------------------------------------------
 // d2 of point p to the centre of its cell, in the order the header states
@@ -176,84 +106,7 @@ __global__ void __launch_bounds__(kRsBlock) ds_emit_kernel(DsArgs a, int32_t *__
 }
 
 // ---- nearest source point ------------------------------------------------------------------------------------
-struct NnGrid {
-  int64_t cap;
-  int32_t *owner;        // [cap]
-  int32_t *count;        // [cap]  points of the slot's cell, 0 = free
-  int4 *key;             // [cap]  (cx, cy, cz, start) of the slots in use
-  uint32_t *slot_of;     // [n_src]
-  int32_t *rank_of;      // [n_src] position inside the cell, in order of arrival
-  float4 *sorted;        // [n_src] (x, y, z, bits of j), cell after cell
-  void *scan_ws;
-  size_t scan_bytes;
-};
-
-static size_t nn_grid_bytes(int64_t n) {
-  const size_t nn = static_cast<size_t>(n > 0 ? n : 1), cap = static_cast<size_t>(table_cap(n));
-  return 2 * align_up(cap * 4) + align_up(cap * 16) + 2 * align_up(nn * 4) + align_up(nn * 16) +
-         align_up(scan_workspace_bytes(static_cast<int64_t>(cap))) + 256;
-}
-
-static bool nn_carve(void *ws, size_t ws_bytes, int64_t n, NnGrid *g) {
-  if (ws == nullptr || ws_bytes < nn_grid_bytes(n)) return false;
-  const size_t nn = static_cast<size_t>(n > 0 ? n : 1);
-  Workspace a(ws, ws_bytes);
-  g->cap = table_cap(n);
-  g->owner = a.take<int32_t>(g->cap);
-  g->count = a.take<int32_t>(g->cap);
-  g->key = a.take<int4>(g->cap);
-  g->slot_of = a.take<uint32_t>(nn);
-  g->rank_of = a.take<int32_t>(nn);
-  g->sorted = a.take<float4>(nn);
-  g->scan_bytes = scan_workspace_bytes(g->cap);
-  g->scan_ws = a.take<char>(g->scan_bytes);
-  return g->scan_ws != nullptr;
-}
-
-__global__ void __launch_bounds__(kRsBlock) nn_insert_kernel(const float *__restrict__ src, int64_t n, double cell,
-                                                            const int32_t *__restrict__ flags, NnGrid g) {
-  if (*flags & (kFlagBadSrc | kFlagNoGrid)) return;               // no grid: every query takes the full scan
-  for (int64_t i = blockIdx.x * static_cast<int64_t>(kRsBlock) + threadIdx.x; i < n;
-       i += static_cast<int64_t>(gridDim.x) * kRsBlock) {
-    int32_t c[3];
-    int64_t s = -1;
-    if (cell_of(src + 3 * i, cell, kNnCellLimit, c))
-      s = table_insert(g.owner, g.cap, src, n, cell, kNnCellLimit, static_cast<int32_t>(i), c);
-    g.slot_of[i] = s < 0 ? 0xFFFFFFFFu : static_cast<uint32_t>(s);
-    g.rank_of[i] = s < 0 ? 0 : atomicAdd(&g.count[s], 1);
-  }
-}
-
-__global__ void __launch_bounds__(kRsBlock) nn_key_kernel(const float *__restrict__ src, int64_t n, double cell,
-                                                         const int32_t *__restrict__ flags, NnGrid g) {
-  if (*flags & (kFlagBadSrc | kFlagNoGrid)) return;
-  for (int64_t s = blockIdx.x * static_cast<int64_t>(kRsBlock) + threadIdx.x; s < g.cap;
-       s += static_cast<int64_t>(gridDim.x) * kRsBlock) {
-    const int32_t o = g.owner[s];
-    int32_t c[3] = {0, 0, 0};
-    if (o >= 0 && o < n) cell_of(src + 3 * static_cast<int64_t>(o), cell, kNnCellLimit, c);
-    g.key[s] = make_int4(c[0], c[1], c[2], g.key[s].w);
-  }
-}
-
-__global__ void __launch_bounds__(kRsBlock) nn_scatter_kernel(const float *__restrict__ src, int64_t n,
-                                                             const int32_t *__restrict__ flags, NnGrid g) {
-  if (*flags & (kFlagBadSrc | kFlagNoGrid)) return;
-  for (int64_t i = blockIdx.x * static_cast<int64_t>(kRsBlock) + threadIdx.x; i < n;
-       i += static_cast<int64_t>(gridDim.x) * kRsBlock) {
-    const uint32_t s = g.slot_of[i];
-    if (static_cast<int64_t>(s) >= g.cap) continue;
-    const int64_t pos = static_cast<int64_t>(g.key[s].w) + g.rank_of[i];
-    if (pos < 0 || pos >= n) continue;
-    g.sorted[pos] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], __int_as_float(static_cast<int32_t>(i)));
-  }
-}
-
-__device__ __forceinline__ double nn_d2(double qx, double qy, double qz, float sx, float sy, float sz) {
-  const double dx = qx - static_cast<double>(sx), dy = qy - static_cast<double>(sy), dz = qz - static_cast<double>(sz);
-  return (dx * dx + dy * dy) + dz * dz;
-}
-
+// (the grid, its build kernels and nn_d2: point_grid.h)
 __device__ __forceinline__ void nn_write(int64_t q, double d2, int32_t j, double max_dist, int32_t *__restrict__ index,
                                         double *__restrict__ dist2) {
   if (j < 0 || (max_dist >= 0.0 && d2 > max_dist * max_dist)) {
@@ -555,18 +408,8 @@ int sg_nearest_build(const float *src, int n_src, double cell, void *grid, size_
   f.add(g.owner, static_cast<size_t>(g.cap) * 4, 0xff);
   f.add(g.count, static_cast<size_t>(g.cap) * 4, 0);
   fill_many(f, stream);
-  const int grid_n = grid_for(n_src, kRsBlock, 4096);
-  rs_validate_kernel<<<grid_n, kRsBlock, 0, stream>>>(src, n_src, cell, kNnCellLimit, kFlagBadSrc, kFlagNoGrid, meta + 1);
-  nn_insert_kernel<<<grid_n, kRsBlock, 0, stream>>>(src, n_src, cell, meta + 1, g);
-  // the starts of the cells go straight into the fourth component of the keys; nn_key_kernel adds the cells
-  const int32_t *count = g.count;
-  int4 *key = g.key;
-  const int rc = exclusive_scan([count] __device__(int64_t s) { return count[s]; },
-                                [key] __device__(int64_t s, int v) { key[s].w = v; }, g.cap, nullptr, g.scan_ws,
-                                g.scan_bytes, stream);
+  const int rc = nn_grid_build(src, n_src, cell, g, meta + 1, 4096, stream);
   if (rc != SG_OK) return rc;
-  nn_key_kernel<<<grid_for(g.cap, kRsBlock, 4096), kRsBlock, 0, stream>>>(src, n_src, cell, meta + 1, g);
-  nn_scatter_kernel<<<grid_n, kRsBlock, 0, stream>>>(src, n_src, meta + 1, g);
   return check_launch("sg_nearest_build");
 }
 

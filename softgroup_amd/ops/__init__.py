@@ -8,6 +8,8 @@ from .losses import assign_proposals, instance_losses, point_wise_loss  # noqa: 
 from .nms import mask_bits_from_runs, mask_nms, mask_nms_numpy  # noqa: F401
 from .resample import (grid_downsample, mask_bits_gather, mask_runs_from_bits,  # noqa: F401
                        nearest_index)
+from .geometry import (grow_segments, grow_segments_numpy, knn, knn_numpy, point_normals,  # noqa: F401
+                       point_normals_numpy)
 from .split import mask_components, mask_components_numpy  # noqa: F401
 from .superpoint import (SuperpointIndex, mask_snap, mask_snap_numpy, superpoint_index,  # noqa: F401
                          superpoint_index_numpy, superpoint_vote, superpoint_vote_numpy)
