@@ -28,7 +28,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..spconv import pytorch as spconv
-from ..util import cuda_cast, force_fp32, to_host, to_host_begin, to_host_end, rle_decode, rle_encode_many, rle_encode_runs, rle_text_to_dicts
+from ..util import cuda_cast, force_fp32, to_host, to_host_begin, to_host_end, rle_decode, rle_encode_many, rle_encode_runs
+from ..util.masks import rle_dicts_from_runs_device
 from ..util.lazy import LazyResults, worker as lazy_worker
 from ..spconv.unet_exec import UNetExecutor
 from ..spconv.unet_train import UNetTrainExecutor
@@ -977,17 +978,9 @@ class SoftGroup(nn.Module):
                                          L.stream()), 'sg_instance_runs')
             # the "start len ..." text is written on the device too: what travels to the host is the
             # text itself and one offset per instance
-            tcap = int(lib.sg_rle_format_device_text_bytes(cap, n_out))
-            text = torch.empty(tcap, dtype=torch.uint8, device=dev)
-            text_off = torch.empty(n_kept + 1, dtype=torch.int64, device=dev)
-            ws = L.workspace(lib.sg_rle_format_device_workspace_bytes(cap), dev)
-            L.check(lib.sg_rle_format_device(L.ptr(starts), L.ptr(ends), L.ptr(bounds), n_kept, cap,
-                                             n_out, L.ptr(text), tcap, L.ptr(text_off), L.ptr(ws),
-                                             ws.numel(), L.stream()), 'sg_rle_format_device')
+            masks = rle_dicts_from_runs_device(starts, ends, bounds, n_kept, n_out, dev)
             cls_pred = kept[:, 0] + 1
             score_pred = host[2][kept[:, 1], kept[:, 0]]
-            o = text_off.cpu().tolist()
-            masks = rle_text_to_dicts(n_out, text, o)
             kept_k = range(n_kept)
             if nms is not None:     # bit rows from the runs still on the device, then sg_mask_nms
                 from ..ops import nms as MN

@@ -33,6 +33,8 @@ import math
 
 import numpy as np
 
+from ._args import _host, _is_cuda, _max_dist, _upload, _xyz_device, _xyz_numpy, choose_backend
+
 __all__ = ['knn', 'knn_numpy', 'knn_default_cell', 'point_normals', 'point_normals_numpy', 'grow_segments',
            'grow_segments_numpy', 'auto_backend', 'MAX_K', 'MAX_SHELL', 'MAX_LISTED']
 
@@ -52,59 +54,13 @@ _AUTO = {'knn': 'device', 'normals': 'device', 'grow': 'device'}
 
 def auto_backend(backend, what):
     """'device' or 'numpy' for one of the operations of ``_AUTO``"""
-    if backend not in ('auto', 'device', 'numpy'):
-        raise ValueError(f"backend {backend!r}: one of 'auto', 'device', 'numpy'")
-    if backend == 'auto':
-        import torch
-        backend = _AUTO[what] if torch.cuda.is_available() else 'numpy'
-    return backend
-
-
-def _host(a):
-    import torch
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-
-def _is_cuda(a):
-    import torch
-    return torch.is_tensor(a) and a.is_cuda
-
-
-def _upload(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).cuda()
-
-
-def _xyz_numpy(xyz):
-    xyz = np.ascontiguousarray(_host(xyz), dtype=np.float32)
-    if xyz.ndim != 2 or xyz.shape[1] != 3:
-        raise ValueError('xyz: an array [n, 3]')
-    return xyz
-
-
-def _xyz_device(xyz):
-    import torch
-    if xyz.dim() != 2 or xyz.size(1) != 3:
-        raise ValueError('xyz: a tensor [n, 3]')
-    if xyz.size(0) >= 2**31:
-        raise ValueError('xyz: fewer than 2**31 points')
-    return xyz.detach().to(torch.float32).contiguous()
+    return choose_backend(backend, _AUTO[what])
 
 
 def _k(k):
     if int(k) != k or not 1 <= int(k) <= MAX_K:
         raise ValueError(f'k {k!r}: an integer in 1 .. {MAX_K}')
     return int(k)
-
-
-def _max_dist(max_dist):
-    if max_dist is None:
-        return -1.0
-    max_dist = float(max_dist)
-    if not max_dist >= 0.0:
-        raise ValueError(f'max_dist {max_dist!r}: None or a number >= 0')
-    return max_dist
 
 
 def _cell(cell):

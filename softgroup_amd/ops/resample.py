@@ -20,6 +20,8 @@ import ctypes as C
 
 import numpy as np
 
+from ._args import _max_dist, _upload, _words, _xyz_device, _xyz_numpy, choose_backend
+
 __all__ = ['grid_downsample', 'grid_downsample_numpy', 'nearest_index', 'nearest_index_numpy', 'nearest_default_cell',
            'mask_bits_gather', 'mask_bits_gather_numpy', 'mask_runs_from_bits', 'mask_runs_from_bits_numpy',
            'mask_runs_supported', 'auto_backend']
@@ -35,12 +37,7 @@ _AUTO = {'nearest': 'device', 'voxel': 'device', 'masks': 'device'}
 
 def auto_backend(backend, what):
     """'device' or 'numpy' for one of the operations of ``_AUTO``"""
-    if backend not in ('auto', 'device', 'numpy'):
-        raise ValueError(f"backend {backend!r}: one of 'auto', 'device', 'numpy'")
-    if backend == 'auto':
-        import torch
-        backend = _AUTO[what] if torch.cuda.is_available() else 'numpy'
-    return backend
+    return choose_backend(backend, _AUTO[what])
 
 
 def _pick(pick):
@@ -54,31 +51,6 @@ def _voxel(voxel):
     if not (voxel > 0.0 and np.isfinite(voxel)):
         raise ValueError(f'voxel size {voxel!r}: a finite number > 0')
     return voxel
-
-
-def _xyz_numpy(xyz, what='xyz'):
-    import torch
-    if torch.is_tensor(xyz):
-        xyz = xyz.detach().cpu().numpy()
-    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
-    if xyz.ndim != 2 or xyz.shape[1] != 3:
-        raise ValueError(f'{what}: an array [n, 3]')
-    return xyz
-
-
-def _upload(a):
-    """CUDA tensor of a host array (a read-only array is copied first: torch cannot wrap one)"""
-    import torch
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).cuda()
-
-
-def _xyz_device(xyz, what='xyz'):
-    import torch
-    if xyz.dim() != 2 or xyz.size(1) != 3:
-        raise ValueError(f'{what}: a tensor [n, 3]')
-    if xyz.size(0) >= 2**31:
-        raise ValueError(f'{what}: fewer than 2**31 points')
-    return xyz.to(torch.float32).contiguous()
 
 
 # ---- voxel-grid downsample -----------------------------------------------------------------------------------------
@@ -149,15 +121,6 @@ def nearest_default_cell(lo, hi, n_src):
     lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
     hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
     return float(L.lib().sg_nearest_default_cell(C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data), int(n_src)))
-
-
-def _max_dist(max_dist):
-    if max_dist is None:
-        return -1.0
-    max_dist = float(max_dist)
-    if not max_dist >= 0.0:
-        raise ValueError(f'max_dist {max_dist!r}: None or a number >= 0')
-    return max_dist
 
 
 def nearest_index_numpy(src, query, cell=None, max_dist=None, return_dist=False, chunk=1024):
@@ -249,10 +212,6 @@ def nearest_index(src, query, cell=None, max_dist=None, return_dist=False, retur
 
 
 # ---- masks -----------------------------------------------------------------------------------------------------------
-def _words(n):
-    return (int(n) + 31) // 32
-
-
 def mask_bits_gather_numpy(bits, n_src, index):
     """packed rows (any integer dtype, [n, >= ceil(n_src / 8)] bytes, little-endian bit order) through ``index``
     -> uint8 [n, 4 * ceil(n_out / 32)], the bytes of the gathered bit rows (``unpackbits``, a take, ``packbits``)"""

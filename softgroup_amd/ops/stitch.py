@@ -22,6 +22,7 @@ are held to byte for byte.
 """
 import numpy as np
 
+from ._args import _words, _xyz_device, _xyz_numpy, choose_backend
 from .nms import _measure, _popcount
 
 __all__ = ['auto_backend', 'tile_assign', 'tile_assign_numpy', 'tile_shared', 'tile_shared_numpy', 'mask_cross_links',
@@ -41,16 +42,7 @@ _AUTO = {'tiles': 'device', 'stitch': 'device'}
 
 def auto_backend(backend, what):
     """'device' or 'numpy' for one of the operations of ``_AUTO``"""
-    if backend not in ('auto', 'device', 'numpy'):
-        raise ValueError(f"backend {backend!r}: one of 'auto', 'device', 'numpy'")
-    if backend == 'auto':
-        import torch
-        backend = _AUTO[what] if torch.cuda.is_available() else 'numpy'
-    return backend
-
-
-def _words(n):
-    return (int(n) + 31) // 32
+    return choose_backend(backend, _AUTO[what])
 
 
 def _tile_params(size, margin, origin):
@@ -83,7 +75,6 @@ def tile_assign_numpy(xyz, size, margin, origin=None):
     """-> (cells int32 [T, 2] = (cx, cy), tile_off int64 [T + 1], tile_points int32, core_tile int32 [n],
     core_pos int32 [n], origin): ``np.unique`` of the biased cell keys, a ``searchsorted`` per neighbour and one
     ``lexsort`` of the (tile, point) pairs"""
-    from .resample import _xyz_numpy
     size, margin, origin = _tile_params(size, margin, origin)
     xyz = _xyz_numpy(xyz)
     n = xyz.shape[0]
@@ -140,7 +131,6 @@ def tile_assign(xyz, size, margin, origin=None):
     if not (torch.is_tensor(xyz) and xyz.is_cuda):
         return tile_assign_numpy(xyz, size, margin, origin)
     from .. import _lib as L
-    from .resample import _xyz_device
     size, margin, origin = _tile_params(size, margin, origin)
     xyz = _xyz_device(xyz)
     n, dev = xyz.size(0), xyz.device

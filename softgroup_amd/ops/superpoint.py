@@ -23,6 +23,8 @@ build), CPU tensors and numpy arrays the numpy twins.
 """
 import numpy as np
 
+from ._args import _host, choose_backend
+
 __all__ = ['SuperpointIndex', 'superpoint_index', 'superpoint_index_numpy', 'mask_snap', 'mask_snap_numpy',
            'superpoint_vote', 'superpoint_vote_numpy', 'auto_backend', 'MAX_INSTANCES', 'MAX_CLASSES', 'WALK']
 
@@ -41,12 +43,7 @@ _AUTO = {'snap': 'device', 'vote': 'device'}
 
 def auto_backend(backend, what):
     """'device' or 'numpy' for one of the operations of ``_AUTO``"""
-    if backend not in ('auto', 'device', 'numpy'):
-        raise ValueError(f"backend {backend!r}: one of 'auto', 'device', 'numpy'")
-    if backend == 'auto':
-        import torch
-        backend = _AUTO[what] if torch.cuda.is_available() else 'numpy'
-    return backend
+    return choose_backend(backend, _AUTO[what])
 
 
 def _thr_mode(thr, mode):
@@ -111,11 +108,6 @@ class SuperpointIndex:
 
 
 # ---- the definitions -------------------------------------------------------------------------------------------------
-def _host(a):
-    import torch
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-
-
 def superpoint_index_numpy(sp):
     """The definition: ``np.unique`` and a stable argsort -> SuperpointIndex of numpy arrays"""
     sp = _host(sp)

@@ -20,7 +20,7 @@ rules
 
 backends (the masks; the dense arrays are plain gathers where they live)
   'numpy'   decode, take, encode on the host
-  'device'  RLE text -> ``sg_inst_rle_parse`` -> ``sg_mask_bits_from_runs`` (the route of ``util/nms.py``) ->
+  'device'  RLE text -> ``sg_inst_rle_parse`` -> ``sg_mask_bits_from_runs`` (the route of ``util/masks.py``) ->
             ``sg_mask_bits_gather`` -> ``sg_mask_runs_count`` / ``_fill`` -> ``sg_rle_format_device`` ->
             ``rle_text_to_dicts``; RLE strings whose runs are not ascending raise, as in ``nms_instances``
   'auto'    numpy without a GPU; with one, what ``ops.resample._AUTO['masks']`` says; strings whose runs are not
@@ -35,15 +35,13 @@ needs it.
 import numpy as np
 
 from ..ops import resample as RS
-from . import nms as UN
+from . import masks as M
 from .lazy import LazyResults
-from .results import _runs_of
-from .rle import rle_encode_runs, rle_text_to_dicts
+from .rle import rle_encode_runs
 
 __all__ = ['propagate_result']
 
 _GATHERED = {'semantic_preds': None, 'offset_preds': 0, 'panoptic_preds': 0}      # key -> fill (None: ignore_label)
-_FROM_GT = ('semantic_labels', 'instance_labels', 'offset_labels', 'color_feats', 'gt_instances')
 
 
 class _Index:
@@ -102,16 +100,6 @@ def _gather(arr, idx, fill):
     return out
 
 
-def _dense_of(mask, n_src):
-    if isinstance(mask, dict):
-        _, starts, ends = _runs_of(mask)
-        step = np.zeros(n_src + 1, dtype=np.uint8)          # +1 at a start, -1 (mod 256) at an end
-        step[starts] = 1
-        step[ends] = 255
-        return np.cumsum(step[:-1], dtype=np.uint8)
-    return (np.asarray(mask).reshape(-1) != 0).astype(np.uint8)
-
-
 def _masks_numpy(insts, n_src, idx):
     idx = idx.host()
     n_full = idx.size
@@ -120,7 +108,7 @@ def _masks_numpy(insts, n_src, idx):
     out = []
     for inst in insts:
         pad = np.zeros(n_full + 2, dtype=np.int8)
-        pad[1:-1][ok] = _dense_of(inst['pred_mask'], n_src)[src_of]
+        pad[1:-1][ok] = M.dense_of(inst['pred_mask'], n_src)[src_of]
         edge = np.diff(pad)
         starts = np.flatnonzero(edge == 1)
         out.append(rle_encode_runs(n_full, starts, np.flatnonzero(edge == -1) - starts))
@@ -129,34 +117,10 @@ def _masks_numpy(insts, n_src, idx):
 
 def _masks_device(insts, n_src, idx):
     import torch
-
-    from .. import _lib as L
-    lib = L.lib()
     dev = torch.device('cuda', torch.cuda.current_device())
-    n, n_full = len(insts), idx.size
-    check = None
-    if all(isinstance(inst['pred_mask'], dict) for inst in insts):
-        bits, flags, unsorted = UN._bits_from_rle_device(insts, n_src, dev)
-        check = torch.stack([flags[0] != 0, unsorted])
-    else:
-        bits = torch.from_numpy(UN._packed(insts, n_src).view(np.int32)).to(dev)
-    if check is not None:
-        bad_text, bad_order = check.cpu().tolist()
-        if bad_text:
-            raise ValueError('malformed RLE text (a bad character, an odd token count or a run outside the mask)')
-        if bad_order:
-            raise UN._UnsortedRuns("RLE runs that are not ascending and disjoint: use backend='numpy'")
-    d_idx = idx.device(dev).to(torch.int32)
-    out = RS.mask_bits_gather(bits, n_src, d_idx)
-    starts, ends, bounds = RS.mask_runs_from_bits(out, n_full)
-    cap = max(int(starts.numel()), 1)
-    tcap = int(lib.sg_rle_format_device_text_bytes(cap, n_full))
-    text = torch.empty(tcap, dtype=torch.uint8, device=dev)
-    text_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    ws = L.workspace(lib.sg_rle_format_device_workspace_bytes(cap), dev)
-    L.check(lib.sg_rle_format_device(L.ptr(starts), L.ptr(ends), L.ptr(bounds), n, cap, n_full, L.ptr(text), tcap,
-                                     L.ptr(text_off), L.ptr(ws), ws.numel(), L.stream()), 'sg_rle_format_device')
-    return rle_text_to_dicts(n_full, text, text_off.cpu().tolist())
+    bits = M.checked_rows_device(insts, n_src, dev)
+    out = RS.mask_bits_gather(bits, n_src, idx.device(dev).to(torch.int32))
+    return M.rle_dicts_from_bits_device(out, idx.size, dev)
 
 
 def propagate_result(result, index, coords=None, gt=None, ignore_label=-100, backend='auto'):
@@ -176,7 +140,7 @@ def propagate_result(result, index, coords=None, gt=None, ignore_label=-100, bac
             n_src = int(result[key].shape[0])
             break
     if n_src is None and insts:
-        n_src = UN._length(insts)
+        n_src = M.mask_length(insts)
     lo, hi = idx.bounds() if n_full else (0, -1)
     if n_src is None:
         n_src = hi + 1
@@ -191,33 +155,21 @@ def propagate_result(result, index, coords=None, gt=None, ignore_label=-100, bac
             out[key] = _gather(value, idx, ignore_label if _GATHERED[key] is None else _GATHERED[key])
         elif key == 'coords_float':
             if coords is not None:
-                if int(coords.shape[0]) != n_full:
-                    raise ValueError(f'coords: {coords.shape[0]} points for an index of {n_full}')
-                out[key] = coords
-        elif key in _FROM_GT or key == 'pred_instances':
+                out[key] = M.full_cloud_coords(coords, n_full, 'an index')
+        elif key in M._FROM_GT or key == 'pred_instances':
             pass
         else:
             out[key] = value
     if coords is not None and 'coords_float' not in out:
         out['coords_float'] = coords
-    for key in _FROM_GT:
-        if key in gt:
-            out[key] = gt[key]
+    M.take_from_gt(out, gt)
     if insts is not None:
-        if insts and UN._length(insts) != n_src:
-            raise ValueError(f'pred_instances: masks of {UN._length(insts)} points in a result of {n_src} points')
-        if not insts:
-            masks = []
-        elif chosen == 'device' and backend == 'auto' and not RS.mask_runs_supported(len(insts), n_full):
-            masks = _masks_numpy(insts, n_src, idx)      # (more runs than the device's int32 run numbers hold)
-        elif chosen == 'device':
-            try:
-                masks = _masks_device(insts, n_src, idx)
-            except UN._UnsortedRuns:
-                if backend != 'auto':
-                    raise
-                masks = _masks_numpy(insts, n_src, idx)
-        else:
-            masks = _masks_numpy(insts, n_src, idx)
+        if insts and M.mask_length(insts) != n_src:
+            raise ValueError(f'pred_instances: masks of {M.mask_length(insts)} points in a result of {n_src} points')
+        masks = []
+        if insts:
+            if chosen == 'device' and backend == 'auto' and not RS.mask_runs_supported(len(insts), n_full):
+                chosen = 'numpy'                         # (more runs than the device's int32 run numbers hold)
+            masks = M.with_fallback(backend, chosen, _masks_device, _masks_numpy, insts, n_src, idx)
         out['pred_instances'] = [dict(inst, pred_mask=m) for inst, m in zip(insts, masks)]
     return out

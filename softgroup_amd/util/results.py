@@ -35,6 +35,8 @@ from itertools import groupby
 
 import numpy as np
 
+from ..ops._args import choose_backend
+
 __all__ = ['save_npy', 'save_pred_instances', 'save_gt_instances', 'save_panoptic', 'save_results', 'read_mask',
            'read_int_lines', 'load_pred_instances']
 
@@ -51,12 +53,7 @@ _SEMANTIC_ARRAYS = (('coords', 'coords_float'), ('colors', 'color_feats'), ('sem
 
 
 def _backend(backend, kind='write'):
-    if backend not in ('auto', 'device', 'numpy'):
-        raise ValueError(f"backend {backend!r}: one of 'auto', 'device', 'numpy'")
-    if backend == 'auto':
-        import torch
-        backend = _AUTO[kind] if torch.cuda.is_available() else 'numpy'
-    return backend
+    return choose_backend(backend, _AUTO[kind])
 
 
 def _host(a):

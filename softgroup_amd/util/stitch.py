@@ -30,7 +30,7 @@ rules (include/softgroup_hip.h, ``softgroup_amd.ops.stitch``; the numpy backend 
 
 backends (both produce the same strings)
   'numpy'   packed rows per tile, popcounts, a union-find and one sort of the (object, id) pairs on the host
-  'device'  RLE text -> bit rows per tile (the route of ``util/nms.py``) -> ``sg_tile_shared`` ->
+  'device'  RLE text -> bit rows per tile (the route of ``util/masks.py``) -> ``sg_tile_shared`` ->
             ``sg_mask_bits_gather`` onto the shared strip -> ``sg_mask_cross_links`` -> ``sg_stitch_components`` ->
             ``sg_mask_bits_ids_count`` / ``_fill`` -> ``sg_stitch_union_count`` / ``_fill`` ->
             ``sg_rle_format_device``.  No row over the full cloud exists: memory is the tiles' own bit rows plus
@@ -43,24 +43,18 @@ import numpy as np
 
 from ..ops import resample as RS
 from ..ops import stitch as ST
-from . import nms as UN
+from ..ops._args import _host
+from . import masks as M
 from .lazy import LazyResults
-from .rle import rle_encode_runs, rle_text_to_dicts
 
 __all__ = ['stitch_results']
 
 _FROM_CORE = ('semantic_preds', 'offset_preds')
-_FROM_GT = ('semantic_labels', 'instance_labels', 'offset_labels', 'color_feats', 'gt_instances')
 _DROPPED = ('panoptic_preds', )
 
 
 class _OutOfRange(Exception):
     pass
-
-
-def _host(a):
-    import torch
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
 def _from_core(results, key, tiles, n_tile):
@@ -110,7 +104,7 @@ def _merged(objects, insts, masks):
 def _stitch_numpy(per_tile, base, insts, labels, tiles, n_points, thr, measure, min_shared, drop):
     ids_of = [_host(p).astype(np.int64) for p in tiles.point_ids]
     core_tile = _host(tiles.core_tile)
-    rows = [UN._packed(ti, ids_of[t].size) if ti else None for t, ti in enumerate(per_tile)]
+    rows = [M.packed_rows(ti, ids_of[t].size) if ti else None for t, ti in enumerate(per_tile)]
     edges = []
     for a, b in tiles.neighbours():
         if rows[a] is None or rows[b] is None:
@@ -136,17 +130,11 @@ def _stitch_numpy(per_tile, base, insts, labels, tiles, n_points, thr, measure, 
     objects, key = _objects(comp, core_cnt, insts, drop)
     ids = np.concatenate(ids) if ids else np.zeros(0, np.int32)
     starts, ends, bounds = ST.stitch_union_numpy(ids, np.repeat(key, cnt), len(objects), n_points)
-    masks = [rle_encode_runs(n_points, starts[bounds[o]:bounds[o + 1]],
-                             ends[bounds[o]:bounds[o + 1]].astype(np.int64) - starts[bounds[o]:bounds[o + 1]])
-             for o in range(len(objects))]
-    return _merged(objects, insts, masks)
+    return _merged(objects, insts, M.rle_dicts_from_runs_numpy(starts, ends, bounds, n_points))
 
 
 def _stitch_device(per_tile, base, insts, labels, tiles, n_points, thr, measure, min_shared, drop):
     import torch
-
-    from .. import _lib as L
-    lib = L.lib()
     dev = tiles.core_tile.device if tiles.is_cuda else torch.device('cuda', torch.cuda.current_device())
     n_total = len(insts)
     if not ST.stitch_supported(n_total, 0, n_points):
@@ -159,15 +147,10 @@ def _stitch_device(per_tile, base, insts, labels, tiles, n_points, thr, measure,
         d_labels = torch.from_numpy(labels).to(dev)
         bits, checks = [], []
         for t, ti in enumerate(per_tile):
-            n_t = off[t + 1] - off[t]
-            if not ti:
-                bits.append(None)
-            elif all(isinstance(inst['pred_mask'], dict) for inst in ti):
-                b, flags, unsorted = UN._bits_from_rle_device(ti, n_t, dev)
-                bits.append(b)
-                checks.append(torch.stack([flags[0] != 0, unsorted]))
-            else:
-                bits.append(torch.from_numpy(UN._packed(ti, n_t).view(np.int32)).to(dev))
+            b, check = M.rows_device(ti, off[t + 1] - off[t], dev) if ti else (None, None)
+            bits.append(b)
+            if check is not None:
+                checks.append(check)
         # the points every pair of neighbouring tiles shares: all pairs, then ONE read-back of the counts
         pairs = [(a, b) for a, b in tiles.neighbours() if bits[a] is not None and bits[b] is not None]
         counts = torch.zeros(max(len(pairs), 1), dtype=torch.int32, device=dev)
@@ -191,10 +174,7 @@ def _stitch_device(per_tile, base, insts, labels, tiles, n_points, thr, measure,
         check = torch.stack(checks).any(0).int() if checks else torch.zeros(2, dtype=torch.int32, device=dev)
         back = torch.cat([comp, cnt, core_cnt, check]).cpu().numpy()      # the one small read-back
         comp, cnt, core_cnt = back[:n_total], back[n_total:2 * n_total], back[2 * n_total:3 * n_total]
-        if back[3 * n_total]:
-            raise ValueError('malformed RLE text (a bad character, an odd token count or a run outside the mask)')
-        if back[3 * n_total + 1]:
-            raise UN._UnsortedRuns("RLE runs that are not ascending and disjoint: use backend='numpy'")
+        M.raise_bad_rle(back[3 * n_total], back[3 * n_total + 1])
         total = int(cnt.astype(np.int64).sum())
         if not ST.stitch_supported(n_total, total, n_points):
             raise _OutOfRange(f'{total} mask points')
@@ -213,18 +193,9 @@ def _stitch_device(per_tile, base, insts, labels, tiles, n_points, thr, measure,
                 ST.mask_bits_ids_fill(b, off[t + 1] - off[t], ids_of[t], n_points, d_off[base[t]:base[t + 1]],
                                       d_key[base[t]:base[t + 1]], ids, keys, meta)
         starts, ends, bounds = ST.stitch_union(ids, keys, n_obj, n_points)
-        cap = max(int(starts.numel()), 1)
-        tcap = int(lib.sg_rle_format_device_text_bytes(cap, n_points))
-        text = torch.empty(tcap, dtype=torch.uint8, device=dev)
-        text_off = torch.empty(n_obj + 1, dtype=torch.int64, device=dev)
-        ws = L.workspace(lib.sg_rle_format_device_workspace_bytes(cap), dev)
-        L.check(lib.sg_rle_format_device(L.ptr(starts), L.ptr(ends), L.ptr(bounds), n_obj, cap, n_points, L.ptr(text),
-                                         tcap, L.ptr(text_off), L.ptr(ws), ws.numel(), L.stream()),
-                'sg_rle_format_device')
-        back = torch.cat([text_off, meta.long()]).cpu().tolist()
-        if back[-1]:
+        masks, flag = M.rle_dicts_from_runs_device(starts, ends, bounds, n_obj, n_points, dev, extra=meta)
+        if flag[0]:
             raise ValueError('stitch_results: a point id of the tiles outside the cloud')
-        masks = rle_text_to_dicts(n_points, text, back[:-1])
     return _merged(objects, insts, masks)
 
 
@@ -253,24 +224,21 @@ def stitch_results(results, tiles, coords=None, gt=None, thr=0.5, measure='iou',
     for key, value in dict.items(first):
         if key in _FROM_CORE:
             out[key] = _from_core(results, key, tiles, n_tile)
-        elif key in _DROPPED or key in _FROM_GT or key in ('pred_instances', 'coords_float'):
+        elif key in _DROPPED or key in M._FROM_GT or key in ('pred_instances', 'coords_float'):
             pass
         else:
             out[key] = value
     if coords is not None:
-        if int(coords.shape[0]) != n_points:
-            raise ValueError(f'coords: {coords.shape[0]} points for a cloud of {n_points}')
-        out['coords_float'] = coords
-    for key in _FROM_GT:
-        if key in gt:
-            out[key] = gt[key]
+        out['coords_float'] = M.full_cloud_coords(coords, n_points, 'a cloud')
+    M.take_from_gt(out, gt)
     if not any('pred_instances' in r for r in results):
         return out
     per_tile = [list(r['pred_instances']) if 'pred_instances' in r else [] for r in results]
     base = [0]
     for t, ti in enumerate(per_tile):
-        if ti and UN._length(ti) != n_tile[t]:
-            raise ValueError(f'pred_instances of tile {t}: masks of {UN._length(ti)} points, the tile has {n_tile[t]}')
+        if ti and M.mask_length(ti) != n_tile[t]:
+            raise ValueError(f'pred_instances of tile {t}: masks of {M.mask_length(ti)} points, '
+                             f'the tile has {n_tile[t]}')
         base.append(base[-1] + len(ti))
     insts = [inst for ti in per_tile for inst in ti]
     labels = np.array([int(inst['label_id']) for inst in insts], dtype=np.int64).astype(np.int32)
@@ -286,7 +254,7 @@ def stitch_results(results, tiles, coords=None, gt=None, thr=0.5, measure='iou',
                 raise L.SoftGroupHipError(f'stitch_results: {e}: outside the supported range (at most '
                                           f'{ST.MAX_INSTANCES} tile instances, fewer than 2**31 mask points and points)')
             out['pred_instances'] = _stitch_numpy(*args)
-        except UN._UnsortedRuns:
+        except M.UnsortedRuns:
             if backend != 'auto':
                 raise
             out['pred_instances'] = _stitch_numpy(*args)

@@ -11,7 +11,7 @@ spot -- on the device when it is a CUDA tensor or the device backend runs, so a 
 
 backends
   'numpy'   packed rows, ``mask_snap_numpy`` / ``superpoint_vote_numpy``, runs by ``np.diff`` on the host
-  'device'  RLE text -> ``sg_inst_rle_parse`` -> ``sg_mask_bits_from_runs`` (the route of ``util/nms.py``; dense
+  'device'  RLE text -> ``sg_inst_rle_parse`` -> ``sg_mask_bits_from_runs`` (the route of ``util/masks.py``; dense
             masks are packed on the host and uploaded) -> ``sg_mask_snap`` -> ``sg_mask_runs_count`` / ``_fill`` ->
             ``sg_rle_format_device`` -> ``rle_text_to_dicts``; labels through ``sg_superpoint_vote``.  RLE strings
             whose runs are not ascending raise, as in ``nms_instances``; so do more than 256 classes
@@ -25,13 +25,10 @@ import numpy as np
 
 from ..ops import resample as RS
 from ..ops import superpoint as SP
-from . import nms as UN
+from . import masks as M
 from .lazy import LazyResults
-from .rle import rle_encode_runs, rle_text_to_dicts
 
 __all__ = ['snap_instances', 'refine_result', 'load_scannet_segs']
-
-_CARRIED = ('scan_id', 'label_id', 'conf')
 
 
 def load_scannet_segs(path):
@@ -89,51 +86,30 @@ def _min_npoint(min_npoint):
     return int(min_npoint)
 
 
-def _outputs(insts, keep, rle_masks, dense_rows):
-    """new dicts of the kept instances: RLE in gives RLE out, a dense mask in gives a bool array out"""
-    out = []
-    for g, s in enumerate(keep):
-        src = insts[s]
-        mask = rle_masks[g] if isinstance(src['pred_mask'], dict) else dense_rows(g)
-        out.append(dict({k: src[k] for k in _CARRIED if k in src}, pred_mask=mask))
-    return out
-
-
-def _dense_row(bits_host, n_points):
-    rows = bits_host.view(np.uint8).reshape(bits_host.shape[0], -1)
-    return lambda g: np.unpackbits(rows[g], bitorder='little')[:n_points].astype(bool)
+def _outputs(insts, keep, bits_host, n_points):
+    """new dicts of the kept instances from their rows on the host: RLE in gives RLE out, a dense mask in gives a
+    bool array out"""
+    rows = bits_host.view(np.uint8)
+    rle = [None] * len(keep)
+    if any(isinstance(insts[s]['pred_mask'], dict) for s in keep):
+        rle = M.rle_dicts_from_bits_numpy(bits_host, n_points)
+    return [M.carried(insts[s], rle[g] if isinstance(insts[s]['pred_mask'], dict) else
+                      np.unpackbits(rows[g], bitorder='little')[:n_points].astype(bool))
+            for g, s in enumerate(keep)]
 
 
 def _snap_numpy(insts, n_points, seg, thr, mode, min_npoint):
-    out_bits, npoint = SP.mask_snap_numpy(UN._packed(insts, n_points), n_points, seg.host(), thr, mode)
+    out_bits, npoint = SP.mask_snap_numpy(M.packed_rows(insts, n_points), n_points, seg.host(), thr, mode)
     keep = np.flatnonzero(npoint >= min_npoint).tolist()
-    out_bits = np.ascontiguousarray(out_bits[keep])
-    masks = [None] * len(keep)
-    if any(isinstance(insts[s]['pred_mask'], dict) for s in keep):
-        starts, ends, bounds = RS.mask_runs_from_bits_numpy(out_bits, n_points)
-        masks = [rle_encode_runs(n_points, starts[bounds[g]:bounds[g + 1]],
-                                 ends[bounds[g]:bounds[g + 1]] - starts[bounds[g]:bounds[g + 1]])
-                 for g in range(len(keep))]
-    return _outputs(insts, keep, masks, _dense_row(out_bits, n_points))
+    return _outputs(insts, keep, np.ascontiguousarray(out_bits[keep]), n_points)
 
 
 def _snap_device(insts, n_points, seg, thr, mode, min_npoint):
     import torch
-
-    from .. import _lib as L
-    lib = L.lib()
     dev = torch.device('cuda', torch.cuda.current_device())
     n = len(insts)
     all_rle = all(isinstance(inst['pred_mask'], dict) for inst in insts)
-    if all_rle:
-        bits, flags, unsorted = UN._bits_from_rle_device(insts, n_points, dev)
-        bad_text, bad_order = torch.stack([flags[0] != 0, unsorted]).cpu().tolist()
-        if bad_text:
-            raise ValueError('malformed RLE text (a bad character, an odd token count or a run outside the mask)')
-        if bad_order:
-            raise UN._UnsortedRuns("RLE runs that are not ascending and disjoint: use backend='numpy'")
-    else:
-        bits = torch.from_numpy(UN._packed(insts, n_points).view(np.int32)).to(dev)
+    bits = M.checked_rows_device(insts, n_points, dev)
     out_bits, npoint = SP.snap_device_raw(bits.data_ptr() if bits.numel() else None, n, n_points, seg.device(dev), thr,
                                           mode, dev)
     keep = list(range(n))
@@ -144,26 +120,9 @@ def _snap_device(insts, n_points, seg, thr, mode, min_npoint):
     if not keep:
         return []
     if not all_rle:
-        host = out_bits.cpu().numpy()
-        masks = [None] * len(keep)
-        if any(isinstance(insts[s]['pred_mask'], dict) for s in keep):
-            starts, ends, bounds = RS.mask_runs_from_bits_numpy(host, n_points)
-            masks = [rle_encode_runs(n_points, starts[bounds[g]:bounds[g + 1]],
-                                     ends[bounds[g]:bounds[g + 1]] - starts[bounds[g]:bounds[g + 1]])
-                     for g in range(len(keep))]
-        return _outputs(insts, keep, masks, _dense_row(host, n_points))
-    with torch.cuda.device(dev):
-        starts, ends, bounds = RS.mask_runs_from_bits(out_bits, n_points)
-        cap = max(int(starts.numel()), 1)
-        tcap = int(lib.sg_rle_format_device_text_bytes(cap, n_points))
-        text = torch.empty(tcap, dtype=torch.uint8, device=dev)
-        text_off = torch.empty(len(keep) + 1, dtype=torch.int64, device=dev)
-        ws = L.workspace(lib.sg_rle_format_device_workspace_bytes(cap), dev)
-        L.check(lib.sg_rle_format_device(L.ptr(starts), L.ptr(ends), L.ptr(bounds), len(keep), cap, n_points,
-                                         L.ptr(text), tcap, L.ptr(text_off), L.ptr(ws), ws.numel(), L.stream()),
-                'sg_rle_format_device')
-        masks = rle_text_to_dicts(n_points, text, text_off.cpu().tolist())
-    return _outputs(insts, keep, masks, None)
+        return _outputs(insts, keep, out_bits.cpu().numpy(), n_points)
+    masks = M.rle_dicts_from_bits_device(out_bits, n_points, dev)
+    return [M.carried(insts[s], m) for s, m in zip(keep, masks)]
 
 
 def snap_instances(pred_instances, superpoints, thr=0.5, mode='snap', min_npoint=0, backend='auto'):
@@ -180,18 +139,11 @@ def snap_instances(pred_instances, superpoints, thr=0.5, mode='snap', min_npoint
     insts = list(pred_instances)
     if not insts:
         return []
-    n_points = UN._length(insts)
-    seg = _segments(superpoints)
-    args = (insts, n_points, seg, thr, mode, min_npoint)
+    n_points = M.mask_length(insts)
     if chosen == 'device' and backend == 'auto' and not RS.mask_runs_supported(len(insts), n_points):
         chosen = 'numpy'                                    # (more runs than the device's int32 run numbers hold)
-    if chosen == 'device':
-        try:
-            return _snap_device(*args)
-        except UN._UnsortedRuns:
-            if backend != 'auto':
-                raise
-    return _snap_numpy(*args)
+    return M.with_fallback(backend, chosen, _snap_device, _snap_numpy, insts, n_points, _segments(superpoints), thr,
+                           mode, min_npoint)
 
 
 def _vote(labels, seg, n_classes, ignore_label, backend):

@@ -40,8 +40,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from .results import (_POW10, _THREADS, _Stage, _Writer, _backend, _host, _read_bytes, _runs_of, read_int_lines,
-                      read_mask)
+from ..ops._args import choose_backend
+from .results import _POW10, _THREADS, _Stage, _Writer, _host, _read_bytes, _runs_of, read_int_lines, read_mask
 
 __all__ = ['TASKS', 'INSTANCE_PALETTE', 'SCANNET_CLASS_PALETTE', 'get_coords_color', 'colors_from_result',
            'write_ply', 'save_visualizations']
@@ -84,8 +84,7 @@ _HEADER = ('ply \nformat ascii 1.0\nelement vertex %d\nproperty float x\npropert
 
 
 def _choose(backend, kind):
-    chosen = _backend(backend)                     # (validates; 'auto' -> 'numpy' without a GPU)
-    return _AUTO[kind] if backend == 'auto' and chosen != 'numpy' else chosen
+    return choose_backend(backend, _AUTO[kind])
 
 
 def _palette(table, default):

@@ -291,6 +291,7 @@ def test_snap_instances_numpy(rle, mode):
     else:
         assert [f['conf'] for f in few] == [s['conf'] for s in same]
         assert all(np.array_equal(f['pred_mask'], s['pred_mask']) for f, s in zip(few, same))
+    assert snap_instances(insts, sp, 0.5, mode, min_npoint=int(size.max()) + 1, backend='numpy') == []    # all dropped
     assert snap_instances([], sp, backend='numpy') == []
     with pytest.raises(ValueError):
         snap_instances(insts, sp[:-1], backend='numpy')

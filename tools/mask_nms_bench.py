@@ -102,8 +102,8 @@ def main():
         assert got == want, (name, n_masks)
         device_wall = median_s(lambda: nms_instances(insts, THR, backend='device'), args.reps)
         numpy_wall = median_s(lambda: nms_instances(insts, THR, backend='numpy'), max(1, args.reps // 2), sync=False)
-        from softgroup_amd.util import nms as UN
-        packed = UN._packed(insts, n_points)
+        from softgroup_amd.util import masks as UM
+        packed = UM.packed_rows(insts, n_points)
         scores = np.array([i['conf'] for i in insts], np.float32)
         labels = np.array([i['label_id'] for i in insts], np.int32)
         numpy_kernel = median_s(lambda: MN.mask_nms_numpy(packed, n_points, scores, labels, THR),

@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from softgroup_amd import synthetic  # noqa: E402
 from softgroup_amd.ops import split as MS  # noqa: E402
-from softgroup_amd.util import nms as UN  # noqa: E402
+from softgroup_amd.util import masks as UM  # noqa: E402
 from softgroup_amd.util import split_instances  # noqa: E402
 from softgroup_amd.util.rle import rle_encode  # noqa: E402
 
@@ -98,7 +98,7 @@ def main():
             print('.', end='', file=sys.stderr, flush=True)
 
         numpy_wall = median_s(numpy_run, args.reps, sync=False)
-        packed = UN._packed(insts, n_points)
+        packed = UM.packed_rows(insts, n_points)
         pairs = int(np.unpackbits(packed, axis=1, bitorder='little')[:, :n_points].sum())
         bits = torch.from_numpy(packed.view(np.int32)).to(dev)
         out = MS.mask_components(bits, n_points, d_xyz, *par)

@@ -29,7 +29,7 @@ sys.path.insert(0, ROOT)
 from softgroup_amd import synthetic  # noqa: E402
 from softgroup_amd.data import voxel_downsample  # noqa: E402
 from softgroup_amd.ops import superpoint as SP  # noqa: E402
-from softgroup_amd.util import nms as UN  # noqa: E402
+from softgroup_amd.util import masks as UM  # noqa: E402
 from softgroup_amd.util import refine_result, snap_instances  # noqa: E402
 from softgroup_amd.util.rle import rle_encode  # noqa: E402
 
@@ -105,7 +105,7 @@ def main():
         assert (h_idx.n_seg, h_idx.n_valid, h_idx.max_size) == (d_idx.n_seg, d_idx.n_valid, d_idx.max_size)
         for a, b in zip((h_idx.order, h_idx.seg_of, h_idx.seg_start), (d_idx.order, d_idx.seg_of, d_idx.seg_start)):
             assert np.array_equal(a, b.cpu().numpy()), name
-        packed = UN._packed(insts, n_points)
+        packed = UM.packed_rows(insts, n_points)
         bits = torch.from_numpy(packed.view(np.int32)).to(dev)
         h_snap = SP.mask_snap_numpy(packed, n_points, h_idx, THR, MODE)
         d_snap = SP.mask_snap(bits, n_points, d_idx, THR, MODE)
