@@ -219,18 +219,23 @@ __device__ __forceinline__ void walk_chunk(const F &f, int n, float *__restrict_
   }
 }
 
-// Every thread of the workgroup calls this after its stores of a chunk.  old_step is what the chunk read.
-// Single-chunk tensors advance their counter directly.  Otherwise the chunks of a tensor count themselves in
+// CONTRACT: called by every thread of the workgroup from uniform control flow, after its stores of a chunk.
+// old_step is what the chunk read.  Every thread loads the counter itself at the top of the chunk, and the waves
+// of a workgroup are not in step with each other between chunks: a wave that is still on its way into this chunk
+// must not find the counter advanced by a wave that is already through it (above kOptMaxBlocks chunks a workgroup
+// walks several chunks back to back).  So the barrier comes first, for every tensor: behind it the workgroup's
+// loads of this chunk, the counter among them, have returned.
+// Single-chunk tensors then advance their counter directly.  Otherwise the chunks of a tensor count themselves in
 // arrive[t]; the last one advances the counter and zeroes arrive[t] for the next launch.  Every chunk has read
 // the counter (its update depends on it) before it counts itself, so none can read the advanced value.
 __device__ __forceinline__ void chunk_done(const Chunk &k, float old_step, float *__restrict__ step,
                                            int32_t *__restrict__ arrive) {
   const int64_t n_of_tensor = (k.count + kOptChunk - 1) / kOptChunk;
+  __syncthreads();
   if (n_of_tensor <= 1) {
     if (threadIdx.x == 0) *step = old_step + 1.0f;
     return;
   }
-  __syncthreads();      // (the workgroup's loads of this chunk, the counter among them, have returned)
   if (threadIdx.x == 0) {
     const int before = atomicAdd(arrive + k.t, 1);
     if (before == static_cast<int>(n_of_tensor) - 1) {

@@ -6,6 +6,9 @@ inputs) runs in the same test; its largest error against the float64 result, per
 units of ulp(float32) of the float64 value, is E.  The fused path may be at most 2 E + 1 ulp: the
 factor covers a different but equally valid order of the same few float32 operations, the 1 ulp the
 final rounding.  Both figures are printed and written to profiles/optim_parity.txt.
+
+The `*_above_the_launch_caps` cases run the same checks on _sizes_above(): more chunks than one trip of the
+norm, step and scale kernels takes (tests/test_launch_caps_train.py pins the list to the caps in the source).
 """
 import copy
 import math
@@ -47,15 +50,22 @@ def _sizes():
     return [1, 3, 4, 63, 64, 65, 255, 257, c - 1, c, c + 1, 3 * c + 1, 0] + [5] * 700
 
 
+def _sizes_above():
+    """more chunks than one trip of any kernel takes: above kOptMaxBlocks = 2048 workgroups of the step and scale
+    kernels, above twice kOptNormBlocks = 1024 of the norm kernel (a third trip), and the five chunks of the
+    4 * c + 1 tensor on both sides of chunk 2048: its `arrive` count is split across two trips of the walk"""
+    c = O.chunk_elems()
+    return [c + 1, 3 * c + 1] + [5] * 1100 + [1, 63, 257, c - 1] + [5] * 936 + [4 * c + 1, 2 * c, 3]
+
+
+STEP_CAP, NORM_CAP = 2048, 1024      # kOptMaxBlocks, kOptNormBlocks (tests/test_launch_caps_train.py reads them)
 VIEWS = {7: 1, 10: 3}      # tensor index -> element offset of the view into a larger buffer (misaligned start)
 
 
-@pytest.fixture(scope='module')
-def inputs():
+def _make_inputs(sizes, seed):
     """float32 parameters (|x| in 1e-3 .. 10, both signs) and STEPS gradient sets (some elements
     exactly 0) as flat numpy arrays plus the tensor sizes.  Never modified."""
-    rng = np.random.default_rng(1234)
-    sizes = _sizes()
+    rng = np.random.default_rng(seed)
     n = sum(sizes)
     assert n < 300000
     p = (10.0 ** rng.uniform(-3, 1, n) * rng.choice([-1.0, 1.0], n)).astype(np.float32)
@@ -69,11 +79,22 @@ def inputs():
     return dict(sizes=sizes, p=p, grads=grads)
 
 
+@pytest.fixture(scope='module')
+def inputs():
+    return _make_inputs(_sizes(), 1234)
+
+
+@pytest.fixture(scope='module')
+def inputs_above():
+    return _make_inputs(_sizes_above(), 4321)
+
+
 def _split(flat, sizes, views=True):
     """device tensors of `sizes` holding `flat`; two of them views at an odd element offset"""
     out, at = [], 0
+    dev_flat = torch.from_numpy(np.array(flat)).to(DEV)      # (one upload; the tensors are filled on the device)
     for i, n in enumerate(sizes):
-        src = torch.from_numpy(np.array(flat[at:at + n]))
+        src = dev_flat[at:at + n]
         at += n
         off = VIEWS.get(i, 0) if views else 0
         buf = torch.zeros(n + off + 8, dtype=torch.float32, device=DEV)
@@ -159,8 +180,9 @@ def _reference(inputs, name, kw, coef=None):
 STATE_KEYS = {'Adam': ('exp_avg', 'exp_avg_sq'), 'AdamW': ('exp_avg', 'exp_avg_sq'), 'SGD': ('momentum_buffer', )}
 
 
-def _run(inputs, name, kw, fused, before_step=None):
-    """-> per step (p, state0, state1 or None, steps or None) as flat float32 arrays"""
+def _run(inputs, name, kw, fused, before_step=None, all_steps=False):
+    """-> per step (p, state0, state1 or None, steps or None) as flat float32 arrays; the counters of a sample
+    of the tensors, or of all of them"""
     params = _params(inputs)
     cls = O.FUSED_CLASSES[name] if fused else getattr(torch.optim, name)
     opt = cls(params, **kw)
@@ -178,19 +200,21 @@ def _run(inputs, name, kw, fused, before_step=None):
             else:
                 states.append(None)
         steps = None
-        if 'step' in opt.state[live[0]]:
+        if 'step' in opt.state[live[0]] and all_steps:
+            steps = torch.stack([opt.state[p]['step'].reshape(()).float().to(DEV) for p in live]).cpu().numpy()
+            assert steps.shape == (len(live), )
+        elif 'step' in opt.state[live[0]]:
             steps = np.array([float(opt.state[p]['step']) for p in live[:40] + live[-3:]])
         out.append((_flat(live), states, steps))
         opt.zero_grad()
     return out
 
 
-@pytest.mark.parametrize('config', sorted(CONFIGS))
-def test_steps_against_float64(inputs, config):
+def _steps_against_float64(inputs, config, key, all_steps=False):
     name, kw = CONFIGS[config]
     ref = _reference(inputs, name, kw)
     stock = _run(inputs, name, kw, fused=False)
-    fused = _run(inputs, name, kw, fused=True)
+    fused = _run(inputs, name, kw, fused=True, all_steps=all_steps)
     again = _run(inputs, name, kw, fused=True)
     figures, failures = {}, []
     for step in range(STEPS):
@@ -212,8 +236,30 @@ def test_steps_against_float64(inputs, config):
         assert np.array_equal(fused[step][0], again[step][0])
         for a, b in zip(fused[step][1], again[step][1]):
             assert (a is None and b is None) or np.array_equal(a, b)
-    _record(f'steps[{config}]', figures)
+    _record(f'{key}[{config}]', figures)
     assert not failures, failures
+
+
+@pytest.mark.parametrize('config', sorted(CONFIGS))
+def test_steps_against_float64(inputs, config):
+    _steps_against_float64(inputs, config, 'steps')
+
+
+def test_sizes_above_reach_a_second_trip_of_every_chunk_walk():
+    sizes, c = _sizes_above(), O.chunk_elems()
+    chunks = O.plan_chunks(sizes)
+    assert len(chunks) > STEP_CAP and len(chunks) > 2 * NORM_CAP and sum(sizes) < 300000
+    big = sizes.index(4 * c + 1)
+    of_big = np.flatnonzero(chunks[:, 0] == big)
+    assert len(of_big) == 5 and of_big[0] < STEP_CAP <= of_big[-1]            # `arrive` counts in two trips
+    assert np.array_equal(chunks[of_big, 1], c * np.arange(5)) and chunks[of_big[-1], 2] == 1
+    assert all(sizes[i] == 5 for i in VIEWS)                                    # the two misaligned views
+
+
+@pytest.mark.parametrize('config', ['adam_wd1e-4', 'adamw_wd0.01', 'sgd_nesterov_wd'])
+def test_steps_against_float64_above_the_launch_caps(inputs_above, config):
+    """the same rule on _sizes_above(); every tensor's counter is read after every step"""
+    _steps_against_float64(inputs_above, config, 'steps_above', all_steps=True)
 
 
 def _norm64(inputs, step):
@@ -221,8 +267,7 @@ def _norm64(inputs, step):
     return math.sqrt(float(np.sum(g * g)))
 
 
-@pytest.mark.parametrize('where', ['below', 'above'])
-def test_fused_in_clip(inputs, where):
+def _fused_in_clip(inputs, where, key):
     """optimizer.clip_grad_norm: the norm against float64 within 2 ulp (the sum is in double: what is
     left is its rounding to float32 and one sqrt), the update against the float64 formula with the
     float64 clip coefficient, .grad left as it was; torch's clip_grad_norm_ + step is the stock side."""
@@ -261,10 +306,20 @@ def test_fused_in_clip(inputs, where):
         print(f'clip {where} step {step + 1} norm {float(a):.9g} vs {norms[step]:.12g}: {e:.3f} ulp')
         assert e <= 2.0, (step, float(a), norms[step])
         assert torch.equal(a, b)
-    _record(f'clip[{where}]', figures)
+    _record(f'{key}[{where}]', figures)
     for step in range(STEPS):
         es, ef = figures[f'step {step + 1} p']
         assert ef <= 2 * es + 1, (step, es, ef)
+
+
+@pytest.mark.parametrize('where', ['below', 'above'])
+def test_fused_in_clip(inputs, where):
+    _fused_in_clip(inputs, where, 'clip')
+
+
+def test_fused_in_clip_above_the_launch_caps(inputs_above):
+    """grad_norm_kernel in its third trip, the clipped step in its second"""
+    _fused_in_clip(inputs_above, 'below', 'clip_above')
 
 
 def test_fused_in_clip_leaves_grad_alone(inputs):
@@ -279,8 +334,7 @@ def test_fused_in_clip_leaves_grad_alone(inputs):
     assert e <= 2.0, e
 
 
-@pytest.mark.parametrize('where', ['below', 'above'])
-def test_standalone_clip_grad_norm(inputs, where):
+def _standalone_clip_grad_norm(inputs, where, key):
     """clip_grad_norm_ against torch's own function.  Ours: the float32 norm within 2 ulp of float64
     (as above); coef = max_norm / (norm + 1e-6) adds two float32 roundings (0.5 ulp each) and the
     product one more: 2 + 1.5 = 3.5 ulp relative, up to twice that where a value sits just above a
@@ -304,7 +358,7 @@ def test_standalone_clip_grad_norm(inputs, where):
     et, eo = _ulps(np.array([tn]), np.array([norm])), _ulps(np.array([on]), np.array([norm]))
     gt, go = _ulps(tg, want), _ulps(og, want)
     print(f'clip_grad_norm_ {where}: norm torch {et:.3f} ulp, ours {eo:.3f} ulp; grads torch {gt:.3f}, ours {go:.3f}')
-    _record(f'clip_grad_norm_[{where}]', {'norm': (et, eo), 'grads': (gt, go)})
+    _record(f'{key}[{where}]', {'norm': (et, eo), 'grads': (gt, go)})
     assert eo <= 2.0
     assert on == on2 and np.array_equal(og, og2)                      # two runs: the same bits
     if where == 'above':
@@ -322,6 +376,16 @@ def test_standalone_clip_grad_norm(inputs, where):
     _set_grads(q, inputs, 0)
     b = torch.nn.utils.clip_grad_norm_(q, max_norm, norm_type=1.0)
     assert torch.equal(a, b) and all(torch.equal(x.grad, y.grad) for x, y in zip(params, q))
+
+
+@pytest.mark.parametrize('where', ['below', 'above'])
+def test_standalone_clip_grad_norm(inputs, where):
+    _standalone_clip_grad_norm(inputs, where, 'clip_grad_norm_')
+
+
+def test_standalone_clip_grad_norm_above_the_launch_caps(inputs_above):
+    """grad_norm_kernel in its third trip, scale_grads_kernel in its second"""
+    _standalone_clip_grad_norm(inputs_above, 'below', 'clip_grad_norm_above')
 
 
 def test_states_sharing_a_misaligned_start(inputs):
@@ -380,8 +444,7 @@ def test_grad_scale_power_of_two_is_exact(inputs, config):
             assert (a is None and b is None) or np.array_equal(a, b)
 
 
-@pytest.mark.parametrize('config', ['adam_wd1e-4', 'sgd_nesterov_wd'])
-def test_found_inf_writes_nothing(inputs, config):
+def _found_inf_writes_nothing(inputs, config):
     name, kw = CONFIGS[config]
     params = _params(inputs)
     opt = O.FUSED_CLASSES[name](params, **kw)
@@ -411,6 +474,16 @@ def test_found_inf_writes_nothing(inputs, config):
     opt.step()
     assert float(opt.state[params[0]]['step']) == 2.0
     assert not torch.equal(before[0], params[0].detach())
+
+
+@pytest.mark.parametrize('config', ['adam_wd1e-4', 'sgd_nesterov_wd'])
+def test_found_inf_writes_nothing(inputs, config):
+    _found_inf_writes_nothing(inputs, config)
+
+
+@pytest.mark.parametrize('config', ['adam_wd1e-4', 'sgd_nesterov_wd'])
+def test_found_inf_writes_nothing_above_the_launch_caps(inputs_above, config):
+    _found_inf_writes_nothing(inputs_above, config)
 
 
 def test_grad_scaler_loop_matches_stock():
