@@ -1686,6 +1686,59 @@ int sg_stitch_union_fill(int64_t total, int n_obj, int64_t n_points, const void 
                          int32_t *ends, int64_t capacity, sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Several results over ONE cloud combined into one (csrc/ensemble.hip): the passes of test-time augmentation, the
+ * folds of several checkpoints, a tiled next to a thinned result.  K passes (1 <= K <= 32) over the same n points in
+ * the same order; pass p has an integer weight 1 <= w_p, W = sum w_p <= 32767.  The reference has no counterpart.
+ * All of it is opt-in.  softgroup_amd.ops.ensemble's numpy twins are the definition and the device results equal
+ * them byte for byte.  Arithmetic is integer apart from the one IEEE double division of the link rule; atomics are
+ * integer only (OR on adjacency bits, ADD on populations): two calls on the same input give the same bytes.  Every
+ * loop is bounded by an argument, every index read from memory is range-checked before it addresses anything, no
+ * workgroup waits for another.
+ *
+ * LABEL VOTE.  labels int64 [K, n] (device, row p = pass p), weights int32 [K] (device), out int64 [n] (must not
+ * overlap labels).  At point x the label of pass p is COUNTED when it is >= 0 and != ignore_label; count(c) = the
+ * sum of w_p over the passes that say c.  out[x] = the class with the greatest count, the LOWEST class among equal
+ * counts; a point with no counted label keeps labels[0, x].  There is no class cap: the winner is one of the at
+ * most K distinct values, found by comparing the K labels of the point with each other in registers.  The weights
+ * are the caller's to keep inside 1 .. 32767 with W <= 32767 (sums are int32; a weight outside the range changes
+ * counts, it is never an address).  RANGE: 1 <= k <= 32, 0 <= n < 2^31, else SG_ERR_UNSUPPORTED. */
+int sg_label_vote(const int64_t *labels /* [K, n] */, int k, int64_t n, const int32_t *weights /* device [K] */,
+                  int64_t ignore_label, int64_t *out, sg_stream_t stream);
+/* GROUP LINKS over one stacked mask matrix.  bits uint32 [n_total, W], W = ceil(n_bits / 32): the instances of all
+ * passes, numbered g = 0 .. n_total-1 by (pass, list order); labels int32 [n_total]; group int32 [n_total] = the
+ * pass of the row.  Bits at and beyond n_bits are ignored.  Rows g < h are LINKED when group[g] != group[h],
+ * labels[g] == labels[h] and the rule of sg_mask_cross_links holds with ca, cb = the populations of the two rows and
+ * inter = popcount(row g & row h), all over the n_bits points: inter >= min_shared, den > 0 and
+ * (double)inter / (double)den > thr, strictly, den = ca + cb - inter for SG_NMS_IOU, min(ca, cb) for SG_NMS_MIN.
+ * It is the kernel of sg_mask_cross_links on the matrix against itself, with the group test beside the label test
+ * and the tile pairs below the diagonal skipped: ONE launch for all K (K - 1) / 2 pairs of passes.  A link sets bit h
+ * of row g and bit g of row h of adj uint32 [n_total, ceil(n_total / 32)] (integer OR; the caller zeroes adj) --
+ * what sg_stitch_components takes.  RANGE: n_total <= 16384, n_bits < 2^31, else SG_ERR_UNSUPPORTED. */
+int sg_mask_group_links(const uint32_t *bits, int n_total, int64_t n_bits, const int32_t *labels, const int32_t *group,
+                        double thr, int measure, int min_shared, uint32_t *adj, sg_stream_t stream);
+/* MASK VOTE.  The objects are the connected components of the links.  obj_off int32 [n_obj + 1]: object o owns the
+ * entries obj_off[o] .. obj_off[o+1] - 1 of members / member_weight / member_pass, int32 arrays of n_total entries
+ * each (an instance belongs to at most one object) sorted by (object, pass): members[m] = the row g of bits,
+ * member_pass[m] = its pass p, member_weight[m] = w_p.  For object o and point x, v = the sum of w_p over the passes
+ * p that have at least one member of o containing x -- a pass counts ONCE per point, however many of its members
+ * hold the point: the entries of one pass are adjacent, their words are OR-ed and the weight of the first of them is
+ * added once.  Bit x of row o of out_bits uint32 [n_obj, W] is set when v >= need[o] (int32 [n_obj], 1 <= need);
+ * npoint int32 [n_obj] = the population of the row.  Bits at and beyond n_bits are ignored in bits and 0 in
+ * out_bits.  A lane owns one output word, the counts of its 32 points are 15 bit planes (v <= 32767) added by
+ * ripple carry and compared with need from the top plane; one integer atomic per wave into npoint, which the call
+ * zeroes first.
+ * Nothing read from memory addresses anything unchecked: obj_off[o] and obj_off[o+1] are clamped into
+ * [0, n_total] and to ascending order; an entry with members[m] outside [0, n_total), member_pass[m] outside
+ * [0, 32) or member_weight[m] outside [1, 32767] is IGNORED (as if it were not in the list); an object whose
+ * need is outside [1, 32767] gets an empty row; a sum beyond 32767 (only with weights the rules above exclude)
+ * counts as reaching every need.  No error status is raised for any of them.
+ * RANGE: n_total <= 16384, n_obj <= 16384, n_bits < 2^31, else SG_ERR_UNSUPPORTED -- nothing is truncated. */
+int sg_mask_vote(const uint32_t *bits, int n_total, int64_t n_bits, const int32_t *obj_off /* [n_obj + 1] */,
+                 const int32_t *members /* sorted by (object, pass) */, const int32_t *member_weight,
+                 const int32_t *member_pass, const int32_t *need, int n_obj, uint32_t *out_bits, int32_t *npoint,
+                 sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Superpoints for clouds that ship none (csrc/geometry.hip): the exact k nearest neighbours, normal and curvature
  * per point, and the connected components of "same smooth surface" links, whose ids sg_superpoint_index accepts as
  * they are.  The reference has no counterpart.  All of it is opt-in: nothing calls it unless asked.

@@ -224,7 +224,10 @@ SIGNATURES = {
     'sg_stitch_union_workspace_bytes': (_sz, [_i64, _i, _i64]),
     'sg_stitch_union_count': (_i, [_vp, _vp, _i64, _i, _i64, _vp, _vp, _sz, _vp]),
     'sg_stitch_union_fill': (_i, [_i64, _i, _i64, _vp, _sz, _vp, _vp, _i64, _vp]),
-    'sg_knn_default_cell': (_d, [_vp, _vp, _i64, _i]),
+    'sg_label_vote': (_i, [_vp, _i, _i64, _vp, _i64, _vp, _vp]),
+    'sg_mask_group_links': (_i, [_vp, _i, _i64, _vp, _vp, _d, _i, _i, _vp, _vp]),
+    'sg_mask_vote': (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    'sg_knn_default_cell':(_d, [_vp, _vp, _i64, _i]),
     'sg_knn_workspace_bytes': (_sz, [_i64, _i]),
     'sg_knn': (_i, [_vp, _i64, _i, _d, _d, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sg_point_normals': (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),

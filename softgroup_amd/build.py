@@ -42,6 +42,7 @@ SOURCES = [
     ('resample.hip', ['-ffp-contract=off']),
     ('geometry.hip', ['-ffp-contract=off']),
     ('stitch.hip', ['-ffp-contract=off']),
+    ('ensemble.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('optim.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),

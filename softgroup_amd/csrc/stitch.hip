@@ -14,6 +14,7 @@
 // steps, the component rounds after G; every index read from memory is range-checked before it addresses
 // anything.  No workgroup waits for another one: where grids must agree there is another launch.
 #include "common.h"
+#include "cross_links.h"
 #include "radix_sort.h"
 #include "scan.h"
 
@@ -28,7 +29,6 @@ constexpr int32_t kTaBias = 1 << 30;
 constexpr uint64_t kTaEmpty = ~0ull;
 constexpr int kTaFlagInvalid = 1, kTaFlagTiles = 2;
 constexpr int kStMaxInst = 16384;
-constexpr int kClTile = 4;
 constexpr int kCcBlock = 1024;
 constexpr uint32_t kIdsTrash = 0xFFFFu;               // "no object": above every object number, inside 16 sort bits
 
@@ -276,16 +276,7 @@ __global__ void __launch_bounds__(kStBlock) shared_find_kernel(const int32_t *__
 }
 
 // ---- rectangular intersections and links ----------------------------------------------------------------------
-struct ClArgs {
-  const uint32_t *bits_a, *bits_b;
-  const int32_t *labels_a, *labels_b;
-  uint32_t *adj;                         // [n_total, nw] symmetric
-  int32_t *inter_out, *cnt_a_out, *cnt_b_out;
-  double thr;
-  int64_t n_bits, words;
-  int n_a, n_b, base_a, base_b, n_total, nw, measure, min_shared;
-};
-
+// (ClArgs: cross_links.h)
 // One workgroup per pair of 4-row tiles (ti of a, tj of b), lane = word: 8 coalesced loads, 16 popcount(a & b)
 // and 8 population accumulators per lane and step; the four waves split the word range and meet in LDS.
 __global__ void __launch_bounds__(kStBlock) cross_links_kernel(ClArgs a) {
@@ -296,6 +287,7 @@ __global__ void __launch_bounds__(kStBlock) cross_links_kernel(ClArgs a) {
   constexpr int kAcc = kClTile * kClTile + 2 * kClTile;
   for (int64_t p = blockIdx.x; p < nta * ntb; p += gridDim.x) {      // (block-uniform)
     const int ti = static_cast<int>(p / ntb), tj = static_cast<int>(p - ti * ntb);
+    if (a.symmetric && ti > tj) continue;                           // (block-uniform, before the barriers)
     int ra[kClTile], rb[kClTile];
 #pragma unroll
     for (int k = 0; k < kClTile; ++k) {
@@ -344,7 +336,8 @@ __global__ void __launch_bounds__(kStBlock) cross_links_kernel(ClArgs a) {
         const int64_t den = a.measure == 0 ? ca + cb - inter : (ca < cb ? ca : cb);
         const int64_t gi = static_cast<int64_t>(a.base_a) + i, gj = static_cast<int64_t>(a.base_b) + j;
         if (a.adj != nullptr && gi < a.n_total && gj < a.n_total && gi != gj && a.labels_a[i] == a.labels_b[j] &&
-            inter >= a.min_shared && den > 0 && static_cast<double>(inter) / static_cast<double>(den) > a.thr) {
+            (a.group_a == nullptr || a.group_a[i] != a.group_b[j]) && inter >= a.min_shared && den > 0 &&
+            static_cast<double>(inter) / static_cast<double>(den) > a.thr) {
           atomicOr(&a.adj[gi * a.nw + (gj >> 5)], 1u << (gj & 31));
           atomicOr(&a.adj[gj * a.nw + (gi >> 5)], 1u << (gi & 31));
         }
@@ -352,6 +345,11 @@ __global__ void __launch_bounds__(kStBlock) cross_links_kernel(ClArgs a) {
     }
     __syncthreads();
   }
+}
+
+void cross_links_launch(const ClArgs &a, int max_blocks, hipStream_t stream) {
+  const int64_t nta = (a.n_a + kClTile - 1) / kClTile, ntb = (a.n_b + kClTile - 1) / kClTile;
+  cross_links_kernel<<<grid_for(nta * ntb, 1, max_blocks), kStBlock, 0, stream>>>(a);
 }
 
 // ---- connected components -------------------------------------------------------------------------------------
@@ -728,8 +726,8 @@ int sg_mask_cross_links(const uint32_t *bits_a, int n_a, const uint32_t *bits_b,
   a.n_bits = n_bits, a.words = (n_bits + 31) / 32;
   a.n_a = n_a, a.n_b = n_b, a.base_a = base_a, a.base_b = base_b, a.n_total = n_total, a.nw = (n_total + 31) / 32;
   a.measure = measure, a.min_shared = min_shared;
-  const int64_t nta = (n_a + kClTile - 1) / kClTile, ntb = (n_b + kClTile - 1) / kClTile;
-  cross_links_kernel<<<grid_for(nta * ntb, 1, 1 << 16), kStBlock, 0, as_stream(stream_)>>>(a);
+  a.group_a = a.group_b = nullptr, a.symmetric = 0;
+  cross_links_launch(a, 1 << 16, as_stream(stream_));
   return check_launch("sg_mask_cross_links");
 }
 

@@ -411,3 +411,4 @@ from .train import TrainTransform, collate_train_device  # noqa: E402,F401
 from .test import TestTransform, collate_x4_test_device  # noqa: E402,F401
 from .downsample import apply_sample, random_downsample, voxel_downsample  # noqa: E402,F401
 from .tiles import TileSet, tile_cloud  # noqa: E402,F401
+from .tta import apply_tta, tta_scan, tta_transforms  # noqa: E402,F401

@@ -15,3 +15,5 @@ from .superpoint import (SuperpointIndex, mask_snap, mask_snap_numpy, superpoint
                          superpoint_index_numpy, superpoint_vote, superpoint_vote_numpy)
 from .stitch import (mask_cross_links, stitch_components, stitch_union, tile_assign,  # noqa: F401
                      tile_shared)
+from .ensemble import (label_vote, label_vote_numpy, mask_group_links, mask_group_links_numpy,  # noqa: F401
+                       mask_vote, mask_vote_numpy)

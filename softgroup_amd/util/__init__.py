@@ -9,6 +9,7 @@ from .nms import nms_instances  # noqa: F401
 from .split import split_instances  # noqa: F401
 from .propagate import propagate_result  # noqa: F401
 from .stitch import stitch_results  # noqa: F401
+from .ensemble import ensemble_results  # noqa: F401
 from .superpoint import load_scannet_segs, refine_result, snap_instances  # noqa: F401
 from .geometry import make_superpoints  # noqa: F401
 from ..optim import build_optimizer, clip_grad_norm_  # noqa: F401,E402
