@@ -370,13 +370,44 @@ int sg_spconv_gather_conv_f32(const float *in, int num_in_rows, const int32_t *n
                               const uint32_t *tile_mask, const int32_t *nbr_tiles, float *out,
                               void *ws, size_t ws_bytes, sg_stream_t stream);
 
+/* Which launch sg_spconv_gather_conv_f32 would make for a layer of these sizes on the current device,
+ * under the process-wide settings in force (sg_spconv_set_combine, the developer knobs of the
+ * environment): the library's own launch decision -- the launch path consumes the same record -- read
+ * out without launching anything.  Meant for tests, which assert through it that a case reaches the
+ * kernel form it is named for.  have_plan: order, tile_mask and nbr_tiles are given (16-byte aligned);
+ * ws_bytes: as passed to the conv call (0 = no workspace); arithmetic: 0, 1 or 2 as for
+ * sg_spconv_set_arithmetic, -1 = the setting in force.  Reports the stand-alone launch, not the
+ * recording of a layer inside an open conv chain.
+ *   family: 0 scalar kernel (cout % 4 != 0), 1 general tile kernel, 2 persistent kernel on the fp32
+ *     MFMA, 3 persistent kernel, split-precision products, 4 persistent kernel, bf16 operands
+ *   blocks_per_unit, vec: tile kernel -- 32-column blocks per wave (1..4), vectorised gather (cin % 16 == 0)
+ *   variant, nbw, wv, ck, at: families 3 and 4 -- index into the variant table (-1 otherwise), column
+ *     blocks per unit, waves per unit, channels per item, line-wise (1) or fragment-shaped (0) gather
+ *   ksplit, k_per_split, combine: slices of the kernel-offset range (1 = none), offsets per slice,
+ *     partial sums added inside the launch (1) or by the reduce kernel (0; also 0 when ksplit == 1)
+ *   units, col_units, grid, block: work units of the launch, units along cout, workgroups, threads each
+ *   num_cu, occupancy: what the grid of a persistent launch was sized with (0 otherwise) */
+typedef struct sg_conv_launch_info {
+  int family;
+  int blocks_per_unit, vec;
+  int variant, nbw, wv, ck, at;
+  int ksplit, k_per_split, combine;
+  int col_units, grid, block;
+  int num_cu, occupancy;
+  int64_t units;
+} sg_conv_launch_info;
+int sg_spconv_conv_launch_info(int num_out_rows, int num_in_rows, int kvol, int cin, int cout, int have_plan,
+                               size_t ws_bytes, int arithmetic, sg_conv_launch_info *info);
+
 /* Arithmetic of the fp32 sparse convolution's products (process-wide, not thread-safe; meant for
  * tests and A/B measurements): 1 = on the bf16 matrix pipe at fp32 accuracy (operands split three
  * ways, six v_mfma_f32_32x32x16_bf16 per 16-channel slice, fp32 accumulation; dropped terms
  * <= 2^-24 |a b|) -- the default; 0 = v_mfma_f32_32x32x2_f32; 2 = bf16 OPERANDS (activations and
  * weights rounded to nearest-even bf16, one v_mfma_f32_32x32x16_bf16 per slice, fp32 accumulation,
- * fp32 in and out: the precision of gather_conv_bf16 without rounding the stored activations;
- * layers with cin % 32 != 0 keep mode 1); -1 = back to the environment (SG_CONV_SPLIT).  No counterpart in the reference: spconv 2.1 multiplies in fp32 (or fp16 under
+ * fp32 in and out: the precision of gather_conv_bf16 without rounding the stored activations; every
+ * layer the persistent kernel takes, the fragment-shaped gather of cin % 32 != 0 included --
+ * tests/test_conv_ref_gpu.py holds each variant to the float64 result on rounded operands);
+ * -1 = back to the environment (SG_CONV_SPLIT).  No counterpart in the reference: spconv 2.1 multiplies in fp32 (or fp16 under
  * autocast).  Edge behaviour of mode 1: an activation that is Inf, NaN or above the bf16 maximum
  * (3.39e38) yields NaN in every output it touches (x - bf16(x) is Inf - Inf), where fp32 products
  * would give Inf; finite inputs below that are unaffected. */

@@ -89,6 +89,7 @@ SIGNATURES = {
     'sg_spconv_conv_workspace_bytes': (_sz, [_i, _i]),
     'sg_spconv_gather_conv_f32': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_spconv_conv_launch_info': (_i, [_i, _i, _i, _i, _i, _i, _sz, _i, _vp]),
     'sg_spconv_packed_weight_elems_bf16': (_sz, [_i, _i, _i]),
     'sg_spconv_pack_weight_bf16': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'sg_spconv_conv_bf16_workspace_bytes': (_sz, [_i, _i]),

@@ -1760,8 +1760,22 @@ static SplitVariant g_split_variants[kSplitVariants] = {
 // 3-deep operand ring -- 2.31 instead of 2.28 ms of conv time per scan, not kept; what such a wave
 // waits for is its own chain of dependent MFMAs and conversions, not its loads.)
 
-static int launch_persistent_split(ConvArgs a, int num_tiles, long long in_bytes, long long w_bytes,
-                                   hipStream_t stream, bool b16, bool in16) {
+// ---------------------------------------------------------------------------------------------
+// The launch decision of one conv layer: kernel family, decomposition, grid.  ONE function makes it
+// (conv_launch_decide); gather_conv_impl / launch_persistent_split launch what it says and
+// sg_spconv_conv_launch_info reports it, so a test can assert which form a case reaches.
+// ---------------------------------------------------------------------------------------------
+enum { kFamScalar = 0, kFamTile = 1, kFamFp32 = 2, kFamSplit = 3, kFamB16 = 4 };
+struct ConvLaunch {
+  sg_conv_launch_info info;     // what the entry point reports (include/softgroup_hip.h)
+  bool persistent, split, use_at;
+  int num_tiles;
+  long long in_bytes, w_bytes;
+  size_t lds;
+};
+
+// CUs of the device and the occupancy of every split variant (read once)
+static int split_variants_num_cu() {
   static int num_cu = 0;
   static std::once_flag once;
   std::call_once(once, [] {
@@ -1784,24 +1798,29 @@ static int launch_persistent_split(ConvArgs a, int num_tiles, long long in_bytes
     };
     for (SplitVariant &v : g_split_variants) prepare(v);
   });
+  return num_cu;
+}
+
+// the split-precision / bf16-operand persistent kernel: variant, units and grid of a layer whose
+// offset split (d.info.ksplit) is already decided.  chain_open: the calling thread has a conv chain open.
+static void decide_persistent_split(ConvLaunch &d, int K, int Cin, int Cout, bool b16, bool in16, bool chain_open) {
+  const int num_cu = split_variants_num_cu();
+  const int num_tiles = d.num_tiles, ksplit = d.info.ksplit;
+  const long long in_bytes = d.in_bytes;
   static const int nbw_env = getenv("SG_CONV_NBW") ? atoi(getenv("SG_CONV_NBW")) : 2;          // developer knobs
   static const int wv_env = getenv("SG_CONV_WV") ? atoi(getenv("SG_CONV_WV")) : 0;             // force 4 / 8 / 16
   static const float min_rounds = getenv("SG_CONV_ROUNDS") ? atof(getenv("SG_CONV_ROUNDS")) : 2.5f;
   static const int at_env = getenv("SG_CONV_AT") ? atoi(getenv("SG_CONV_AT")) : 1;             // line-wise gather
-  const int NB = (a.Cout + 31) / 32;
+  const int NB = (Cout + 31) / 32;
   // (the line-wise gather forms its addresses with a 24-bit multiply: input rows < 2^24 - 1)
   // and an absent neighbour (-1 -> 0xffffff * row pitch, wrapped to 32 bits) must land past the end
   // of the buffer: row pitches that are not multiples of 256 B (Cin = 96, 160, 224) wrap to just
   // below 2^31, which is inside an input of a few million rows -- those take the fragment-shaped gather
-  const unsigned long long row_bytes = (in16 ? 2ull : 4ull) * a.Cin;
+  const unsigned long long row_bytes = (in16 ? 2ull : 4ull) * Cin;
   const unsigned absent_at = static_cast<unsigned>((0xFFFFFFull * row_bytes) & 0xFFFFFFFFull);
-  const int use_at = ((at_env != 0 || in16) && a.Cin % 32 == 0 && in_bytes / static_cast<long long>(row_bytes) < (1LL << 24) - 1 &&
+  const int use_at = ((at_env != 0 || in16) && Cin % 32 == 0 && in_bytes / static_cast<long long>(row_bytes) < (1LL << 24) - 1 &&
                       static_cast<long long>(absent_at) >= in_bytes) ? 1 : 0;
-  if (in16 && (!use_at || !b16)) {
-    set_error("sg_unet_forward(bf16 rows): a layer with %d input channels / %lld input bytes cannot take the line-wise bf16 gather",
-              a.Cin, in_bytes);
-    return SG_ERR_ARG;
-  }
+  d.use_at = use_at != 0;
   int pick = -1;
   // tiny layers arrive with their offsets split over several units (ksplit > 1, partial sums to the
   // workspace, conv_reduce_kernel afterwards): measured faster than 16 waves on very few units
@@ -1816,21 +1835,21 @@ static int launch_persistent_split(ConvArgs a, int num_tiles, long long in_bytes
   static const int w2_max = getenv("SG_CONV_W2_MAX") ? atoi(getenv("SG_CONV_W2_MAX")) : 108;
   static const int w2_nbw = getenv("SG_CONV_W2_NBW") ? atoi(getenv("SG_CONV_W2_NBW")) : 2;      // A/B knob
   static const float w2_rounds = getenv("SG_CONV_W2_ROUNDS") ? atof(getenv("SG_CONV_W2_ROUNDS")) : 1.5f;
-  const bool use_w2 = wv_env == 2 || (wv_env == 0 && a.K * (a.Cin / 32) <= w2_max);
+  const bool use_w2 = wv_env == 2 || (wv_env == 0 && K * (Cin / 32) <= w2_max);
   // (One wave per unit was measured too: the heaviest tiles -- 27 offsets in a single wave -- then
   // set the span of the big layers, 32->32 x 124 k rows 28.5 -> 32.1 us, 64->64 x 77 k 52 -> 69 us; on
   // the K = 8 strided / inverse convs alone it changes nothing, 2.22 ms per scan either way.)
   for (int i = 0; i < kSplitVariants; ++i) {
     const SplitVariant &v = g_split_variants[i];
     if (v.at != use_at) continue;
-    if (v.wv == 2 && (!use_w2 || a.ksplit > 1 || v.nbw > w2_nbw)) continue;
-    if (a.ksplit > 1) {
+    if (v.wv == 2 && (!use_w2 || ksplit > 1 || v.nbw > w2_nbw)) continue;
+    if (ksplit > 1) {
       // (8 waves per unit on these layers: 2.482 against 2.492 ms per backbone forward, no difference)
       if (v.nbw == 1 && v.wv == 4) { pick = i; break; }
       continue;
     }
     pick = i;                         // (the last candidate of the group stays if none qualifies)
-    if (v.nbw == 2 && (a.Cout % 64 != 0 || nbw_env < 2)) continue;
+    if (v.nbw == 2 && (Cout % 64 != 0 || nbw_env < 2)) continue;
     if (wv_env && v.wv != wv_env) continue;
     const long long units = static_cast<long long>(num_tiles) * (NB / v.nbw);
     if (wv_env || units >= static_cast<long long>((v.wv == 2 ? w2_rounds : min_rounds) * num_cu * (in16 ? v.occ_r16 : b16 ? v.occ_b16 : v.occ))) {
@@ -1840,15 +1859,160 @@ static int launch_persistent_split(ConvArgs a, int num_tiles, long long in_bytes
   }
   // a layer of an open chain: the chain's decomposition (8 waves per unit, one column block, line-wise
   // gather), whether it is recorded or launched by itself
-  const bool chain_layer = t_chain.mode != 0 && use_at != 0;
+  const bool chain_layer = chain_open && use_at != 0;
   if (chain_layer) {
     for (int i = 0; i < kSplitVariants; ++i)
       if (g_split_variants[i].at == 1 && g_split_variants[i].nbw == 1 && g_split_variants[i].wv == kChainWV) pick = i;
   }
   const SplitVariant &v = g_split_variants[pick];
-  a.col_units = NB / v.nbw;
+  sg_conv_launch_info &f = d.info;
+  f.variant = pick; f.nbw = v.nbw; f.wv = v.wv; f.ck = v.ck; f.at = v.at;
+  f.col_units = NB / v.nbw;
+  f.blocks_per_unit = v.nbw;
+  f.units = static_cast<long long>(num_tiles) * f.col_units * ksplit;
+  f.num_cu = num_cu;
+  f.occupancy = in16 ? v.occ_r16 : b16 ? v.occ_b16 : v.occ;
+  // grid: the resident workgroups, a multiple of 8 (unit u runs on XCD u % 8 in every round).  A layer
+  // with fewer units than that gets one workgroup per unit, rounded UP to the next multiple of 8 --
+  // the surplus workgroups leave at once.  (Rounded down, as until round 5, 98 units ran on 96
+  // workgroups and two of them took a second unit: the 18-row layers spent 21.5 k instead of 10.5 k
+  // ticks, the 141-row layers 24.5 k instead of 15 k -- profiles/r06_conv_trace_base.txt.)
+  long long g = static_cast<long long>(num_cu) * f.occupancy;
+  if (g >= 8) g -= g % 8;
+  if (f.units < g) g = f.units >= 8 ? (f.units + 7) / 8 * 8 : f.units;
+  f.grid = static_cast<int>(g);
+  f.block = 64 * v.wv;
+  d.lds = v.lds;
+}
+
+// the arithmetic in force for the calling thread: 0 fp32 MFMA, 1 split precision, 2 bf16 operands
+static int conv_arith_in_force() {
+  static const int split_env = getenv("SG_CONV_SPLIT") ? atoi(getenv("SG_CONV_SPLIT")) : 1;
+  const int arith_ov = t_conv_arith >= 0 ? t_conv_arith : g_arith_override.load(std::memory_order_relaxed);
+  return arith_ov >= 0 ? arith_ov : split_env;
+}
+
+constexpr size_t kFp32PersistentLds = static_cast<size_t>(kWavesPerWg) * 16 * 64 * sizeof(float) +
+                                      2 * kMetaInts * sizeof(int32_t) + 16;
+constexpr int kFp32SliceCh = 16;
+
+// have_plan: order, tile_mask and nbr_tiles are there (nbr_tiles 16-byte aligned); ws_bytes: 0 without a
+// workspace; split_on: conv_arith_in_force() or the caller's choice
+static ConvLaunch conv_launch_decide(int M_out, int num_in_rows, int K, int Cin, int Cout, bool have_plan,
+                                     size_t ws_bytes, int split_on, bool in16, bool chain_open) {
+  ConvLaunch d = {};
+  sg_conv_launch_info &f = d.info;
+  f.variant = -1;
+  f.ksplit = 1;
+  f.k_per_split = K;
+  if (Cout % 4 != 0) {
+    f.family = kFamScalar;
+    f.grid = grid_for(static_cast<int64_t>(M_out) * Cout, 256, 256 * 32);
+    f.block = 256;
+    f.units = static_cast<int64_t>(M_out) * Cout;
+    return d;
+  }
+  const int NB = (Cout + 31) / 32;
+  const int num_tiles = (M_out + kTileRows - 1) / kTileRows;
+  d.num_tiles = num_tiles;
+  d.in_bytes = static_cast<long long>(num_in_rows) * Cin * (in16 ? 2 : 4);
+  d.w_bytes = static_cast<long long>(sg_spconv_packed_weight_elems(K, Cin, Cout)) * 4;
+  const bool persistent = Cin % 16 == 0 && d.in_bytes < (1LL << 31) && num_in_rows > 0 &&
+                          static_cast<long long>(M_out) * Cout * 4 * kMaxK < (1LL << 32) &&
+                          static_cast<long long>(num_tiles) * kTileRows * K * 4 < (1LL << 31) && have_plan;
+  // split-precision path (fp32 products as six bf16 MFMAs, see split3): the default for every layer
+  // the persistent kernel takes with Cin >= SG_CONV_SPLIT_MIN_CIN (SG_CONV_SPLIT=0: the fp32-MFMA
+  // kernel, kept for A/B)
+  static const int split_min_cin = getenv("SG_CONV_SPLIT_MIN_CIN") ? atoi(getenv("SG_CONV_SPLIT_MIN_CIN")) : 16;
+  const bool split = persistent && split_on != 0 && Cin >= split_min_cin;
+  d.persistent = persistent;
+  d.split = split;
+  // ---- decomposition: aim at >= ~2048 waves; the general kernel widens its column block while
+  //      that still fills the chip, the persistent kernel always works on 32-column blocks
+  static const int target_env = getenv("SG_CONV_TARGET") ? atoi(getenv("SG_CONV_TARGET")) : 0;   // developer knob
+  // (the split-precision kernel's units are shorter: it wants half as many offset splits, measured)
+  const int target = target_env > 0 ? target_env : split ? 1024 : 2048;
+  const int waves_per_unit = persistent ? kWavesPerWg : 1;
+  int bpu = 1;
+  if (!persistent) {
+    bpu = NB < 4 ? NB : 4;
+    while (bpu > 1 && static_cast<long long>(num_tiles) * ((NB + bpu - 1) / bpu) < target) --bpu;
+  }
+  const int col_units = (NB + bpu - 1) / bpu;
+  int ksplit = 1;
+  const long long waves = static_cast<long long>(num_tiles) * col_units * waves_per_unit;
+  if (waves < target / 2) {
+    const long long want = (target / 2 + waves - 1) / waves;
+    ksplit = static_cast<int>(want < K ? want : K);
+    const size_t need = static_cast<size_t>(ksplit) * M_out * Cout * sizeof(float);
+    if (ksplit > 1 && ws_bytes < need) ksplit = 1;   // no scratch: stay exact
+  }
+  const int k_per_split = (K + ksplit - 1) / ksplit;
+  ksplit = (K + k_per_split - 1) / k_per_split;
+  f.ksplit = ksplit;
+  f.k_per_split = k_per_split;
+  f.col_units = col_units;
+  f.blocks_per_unit = bpu;
+  f.units = static_cast<long long>(num_tiles) * col_units * ksplit;
+  // offset-split layers of the persistent kernel: partial sums combined inside the launch by the last
+  // workgroup of each (tile, column unit) instead of by conv_reduce_kernel (the default; SG_CONV_COMBINE=0
+  // / sg_spconv_set_combine(0): the separate reduce kernel, same numbers)
+  static const int combine_env = getenv("SG_CONV_COMBINE") ? atoi(getenv("SG_CONV_COMBINE")) : 1;
+  const int combine_ov = g_combine_override.load(std::memory_order_relaxed);
+  f.combine = (combine_ov >= 0 ? combine_ov : combine_env) != 0 && persistent && ksplit > 1 &&
+              static_cast<long long>(num_tiles) * col_units <= kDoneCounters;
+  if (split) {
+    f.family = split_on == 2 ? kFamB16 : kFamSplit;
+    decide_persistent_split(d, K, Cin, Cout, split_on == 2, in16, chain_open);
+  } else if (persistent) {
+    // fp32-MFMA kernel (SG_CONV_SPLIT=0 / sg_spconv_set_arithmetic(0), and layers below
+    // SG_CONV_SPLIT_MIN_CIN): 16-channel slices, 2-deep operand ring, 4 waves per unit, one column
+    // block; as many workgroups as are resident at once (a multiple of 8 so that unit u always runs
+    // on XCD u % 8).  (Rounds 1-3 also carried 4- and 8-deep rings, an 80-VGPR build and 64-column
+    // units of this kernel; none of them was faster and they are gone.)
+    static int num_cu = 0, occ = 0;
+    static std::once_flag once;
+    std::call_once(once, [&] {
+      int dev = 0;
+      hipGetDevice(&dev);
+      hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev);
+      if (num_cu <= 0) num_cu = 256;
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, gather_conv_persistent_kernel<kFp32SliceCh, 2, 0, 5>, 256,
+                                                   kFp32PersistentLds);
+      if (occ < 1) occ = 1;
+    });
+    f.family = kFamFp32;
+    f.nbw = 1; f.wv = kWavesPerWg; f.ck = kFp32SliceCh; f.at = 0;
+    f.num_cu = num_cu;
+    f.occupancy = occ;
+    long long g = static_cast<long long>(num_cu) * occ;
+    if (g >= 8) g -= g % 8;
+    if (f.units < g) g = f.units >= 8 ? (f.units + 7) / 8 * 8 : f.units;      // (see decide_persistent_split)
+    f.grid = static_cast<int>(g);
+    f.block = 256;
+    d.lds = kFp32PersistentLds;
+  } else {
+    f.family = kFamTile;
+    f.vec = (Cin % kCk) == 0;
+    f.grid = static_cast<int>((f.units + kWavesPerWg - 1) / kWavesPerWg);
+    f.block = 256;
+    d.lds = kWavesPerWg * kTileRows * kMaxK * sizeof(int32_t);
+  }
+  return d;
+}
+
+static int launch_persistent_split(ConvArgs a, const ConvLaunch &d, hipStream_t stream, bool b16, bool in16) {
+  const long long in_bytes = d.in_bytes, w_bytes = d.w_bytes;
+  if (in16 && (!d.use_at || !b16)) {
+    set_error("sg_unet_forward(bf16 rows): a layer with %d input channels / %lld input bytes cannot take the line-wise bf16 gather",
+              a.Cin, in_bytes);
+    return SG_ERR_ARG;
+  }
+  const SplitVariant &v = g_split_variants[d.info.variant];
+  const bool chain_layer = t_chain.mode != 0 && d.use_at;
+  a.col_units = d.info.col_units;
   a.blocks_per_unit = v.nbw;
-  const long long units = static_cast<long long>(num_tiles) * a.col_units * a.ksplit;
+  const long long units = d.info.units;
   a.num_units = static_cast<int>(units);
   auto magic = [](unsigned d) { return d <= 1 ? 0u : static_cast<unsigned>((1ULL << 32) / d) + 1u; };
   a.magic_upt = magic(static_cast<unsigned>(a.col_units * a.ksplit));
@@ -1877,14 +2041,7 @@ static int launch_persistent_split(ConvArgs a, int num_tiles, long long in_bytes
   static const int dyn_rounds_env = getenv("SG_CONV_DYN_ROUNDS") ? atoi(getenv("SG_CONV_DYN_ROUNDS")) : 2;
   a.queue = dyn_env ? take_tickets(stream) : nullptr;
   a.dyn_rounds = dyn_rounds_env == 1 ? 1 : 2;
-  // grid: the resident workgroups, a multiple of 8 (unit u runs on XCD u % 8 in every round).  A layer
-  // with fewer units than that gets one workgroup per unit, rounded UP to the next multiple of 8 --
-  // the surplus workgroups leave at once.  (Rounded down, as until round 5, 98 units ran on 96
-  // workgroups and two of them took a second unit: the 18-row layers spent 21.5 k instead of 10.5 k
-  // ticks, the 141-row layers 24.5 k instead of 15 k -- profiles/r06_conv_trace_base.txt.)
-  long long g = static_cast<long long>(num_cu) * (in16 ? v.occ_r16 : b16 ? v.occ_b16 : v.occ);
-  if (g >= 8) g -= g % 8;
-  if (units < g) g = units >= 8 ? (units + 7) / 8 * 8 : units;
+  const long long g = d.info.grid;
   const unsigned ib = static_cast<unsigned>(in_bytes), wb = static_cast<unsigned>(w_bytes);
   if (in16) {
     v.fn_r16<<<static_cast<int>(g), 64 * v.wv, v.lds, stream>>>(a, ib, wb);
@@ -2018,6 +2175,17 @@ size_t sg_spconv_conv_workspace_bytes(int M_out, int Cout) {
   return static_cast<size_t>(kMaxK) * M_out * Cout * sizeof(float) + 256;
 }
 
+int sg_spconv_conv_launch_info(int M_out, int num_in_rows, int K, int Cin, int Cout, int have_plan, size_t ws_bytes,
+                               int arithmetic, sg_conv_launch_info *info) {
+  SG_REQUIRE(info != nullptr && M_out >= 1 && num_in_rows >= 0 && K >= 1 && K <= kMaxK && Cin >= 1 && Cout >= 1 &&
+             arithmetic >= -1 && arithmetic <= 2,
+             "sg_spconv_conv_launch_info: bad arguments (M_out=%d K=%d Cin=%d Cout=%d arithmetic=%d)", M_out, K, Cin,
+             Cout, arithmetic);
+  *info = conv_launch_decide(M_out, num_in_rows, K, Cin, Cout, have_plan != 0, ws_bytes,
+                             arithmetic >= 0 ? arithmetic : conv_arith_in_force(), false, false).info;
+  return SG_OK;
+}
+
 // in16 / out16 / res16: `in` / `out` + `out_act` / `residual` are bf16 rows (the executor's arithmetic 3; the
 // pointers are typed float for the fp32 case only).  Needs the bf16-operand arithmetic and, for in16, the
 // line-wise gather (Cin % 32 == 0); an offset-split layer combines in the launch.
@@ -2050,55 +2218,24 @@ static int gather_conv_impl(const float *in, int num_in_rows, const int32_t *nbr
       if (on) hipEventRecord(g_conv_prof.take(), st);
     }
   } prof_scope(stream, K > 1, M_out, K, Cin, Cout, num_in_rows);     // the 1x1 identity-branch convs are not part of the conv roofline
-  if (Cout % 4 != 0) {
+  const int split_on = conv_arith_in_force();
+  const bool have_plan = order != nullptr && tile_mask != nullptr && nbr_tiles != nullptr &&
+                         reinterpret_cast<uintptr_t>(nbr_tiles) % 16 == 0;      // 16-byte LDS-DMA pieces
+  const ConvLaunch d = conv_launch_decide(M_out, num_in_rows, K, Cin, Cout, have_plan, ws != nullptr ? ws_bytes : 0,
+                                          split_on, in16 != 0, t_chain.mode != 0);
+  const sg_conv_launch_info &f = d.info;
+  if (f.family == kFamScalar) {
     if (t_chain.mode == 2) {
       const int rc = chain_flush();
       if (rc != SG_OK) return rc;
     }
-    gather_conv_scalar_kernel<<<grid_for(static_cast<int64_t>(M_out) * Cout, 256, 256 * 32), 256, 0,
-                                stream>>>(in, nbr, M_out, K, Cin, Cout, w_k8, post_scale, post_shift,
-                                          residual, act_scale, act_shift, out_act, out);
+    gather_conv_scalar_kernel<<<f.grid, f.block, 0, stream>>>(in, nbr, M_out, K, Cin, Cout, w_k8, post_scale, post_shift,
+                                                              residual, act_scale, act_shift, out_act, out);
     return check_launch("sg_spconv_gather_conv_f32(scalar)");
   }
-  const int NB = (Cout + 31) / 32;
-  const int num_tiles = (M_out + kTileRows - 1) / kTileRows;
-  const long long in_bytes_ll = static_cast<long long>(num_in_rows) * Cin * (in16 ? 2 : 4);
-  const long long w_bytes_ll = static_cast<long long>(sg_spconv_packed_weight_elems(K, Cin, Cout)) * 4;
-  const bool persistent = Cin % 16 == 0 && in_bytes_ll < (1LL << 31) && num_in_rows > 0 &&
-                          static_cast<long long>(M_out) * Cout * 4 * kMaxK < (1LL << 32) &&
-                          static_cast<long long>(num_tiles) * kTileRows * K * 4 < (1LL << 31) &&
-                          order != nullptr && tile_mask != nullptr && nbr_tiles != nullptr &&
-                          reinterpret_cast<uintptr_t>(nbr_tiles) % 16 == 0;      // 16-byte LDS-DMA pieces
-  // split-precision path (fp32 products as six bf16 MFMAs, see split3): the default for every layer
-  // the persistent kernel takes with Cin >= SG_CONV_SPLIT_MIN_CIN (SG_CONV_SPLIT=0: the fp32-MFMA
-  // kernel, kept for A/B)
-  static const int split_env = getenv("SG_CONV_SPLIT") ? atoi(getenv("SG_CONV_SPLIT")) : 1;
-  static const int split_min_cin = getenv("SG_CONV_SPLIT_MIN_CIN") ? atoi(getenv("SG_CONV_SPLIT_MIN_CIN")) : 16;
-  const int arith_ov = t_conv_arith >= 0 ? t_conv_arith : g_arith_override.load(std::memory_order_relaxed);
-  const int split_on = arith_ov >= 0 ? arith_ov : split_env;
-  const bool split = persistent && split_on != 0 && Cin >= split_min_cin;
-  // ---- decomposition: aim at >= ~2048 waves; the general kernel widens its column block while
-  //      that still fills the chip, the persistent kernel always works on 32-column blocks
-  static const int target_env = getenv("SG_CONV_TARGET") ? atoi(getenv("SG_CONV_TARGET")) : 0;   // developer knob
-  // (the split-precision kernel's units are shorter: it wants half as many offset splits, measured)
-  const int target = target_env > 0 ? target_env : split ? 1024 : 2048;
-  const int waves_per_unit = persistent ? kWavesPerWg : 1;
-  int bpu = 1;
-  if (!persistent) {
-    bpu = NB < 4 ? NB : 4;
-    while (bpu > 1 && static_cast<long long>(num_tiles) * ((NB + bpu - 1) / bpu) < target) --bpu;
-  }
-  const int col_units = (NB + bpu - 1) / bpu;
-  int ksplit = 1;
-  const long long waves = static_cast<long long>(num_tiles) * col_units * waves_per_unit;
-  if (waves < target / 2) {
-    const long long want = (target / 2 + waves - 1) / waves;
-    ksplit = static_cast<int>(want < K ? want : K);
-    const size_t need = static_cast<size_t>(ksplit) * M_out * Cout * sizeof(float);
-    if (ksplit > 1 && (ws == nullptr || ws_bytes < need)) ksplit = 1;   // no scratch: stay exact
-  }
-  const int k_per_split = (K + ksplit - 1) / ksplit;
-  ksplit = (K + k_per_split - 1) / k_per_split;
+  const bool split = d.split, persistent = d.persistent;
+  const int ksplit = f.ksplit;
+  const long long units = f.units;
 
   ConvArgs a;
   a.in = in; a.nbr = nbr; a.w = w_k8; a.post_scale = post_scale; a.post_shift = post_shift;
@@ -2106,27 +2243,19 @@ static int gather_conv_impl(const float *in, int num_in_rows, const int32_t *nbr
   a.order = order; a.tile_mask = tile_mask; a.nbr_tiles = nbr_tiles;
   a.out = ksplit > 1 ? static_cast<float *>(ws) : out;
   a.M_out = M_out; a.K = K; a.Cin = Cin; a.Cout = Cout;
-  a.col_units = col_units; a.blocks_per_unit = bpu; a.ksplit = ksplit; a.k_per_split = k_per_split;
+  a.col_units = f.col_units; a.blocks_per_unit = f.blocks_per_unit; a.ksplit = ksplit; a.k_per_split = f.k_per_split;
   a.trace = nullptr;
   a.queue = nullptr;
   a.dyn_rounds = 2;
   a.out16 = out16;
   a.res16 = res16;
-  // offset-split layers of the persistent kernel: partial sums combined inside the launch by the last
-  // workgroup of each (tile, column unit) instead of by conv_reduce_kernel (the default; SG_CONV_COMBINE=0
-  // / sg_spconv_set_combine(0): the separate reduce kernel, same numbers)
-  static const int combine_env = getenv("SG_CONV_COMBINE") ? atoi(getenv("SG_CONV_COMBINE")) : 1;
   a.done = nullptr;
   a.out_final = out;
-  const int combine_ov = g_combine_override.load(std::memory_order_relaxed);
-  if ((combine_ov >= 0 ? combine_ov : combine_env) != 0 && persistent && ksplit > 1 &&
-      static_cast<long long>(num_tiles) * col_units <= kDoneCounters)
-    a.done = take_done(stream, static_cast<size_t>(num_tiles) * col_units);
-  const long long units = static_cast<long long>(num_tiles) * col_units * ksplit;
+  if (f.combine) a.done = take_done(stream, static_cast<size_t>(d.num_tiles) * f.col_units);
   a.num_units = static_cast<int>(units);
   auto magic = [](unsigned d) { return d <= 1 ? 0u : static_cast<unsigned>((1ULL << 32) / d) + 1u; };
-  a.magic_upt = magic(static_cast<unsigned>(col_units * ksplit));
-  a.magic_cu = magic(static_cast<unsigned>(col_units));
+  a.magic_upt = magic(static_cast<unsigned>(f.col_units * ksplit));
+  a.magic_cu = magic(static_cast<unsigned>(f.col_units));
   a.magic_nsl = 0;
 
   if (!split && t_chain.mode == 2) {      // not a layer the chain kernel takes
@@ -2139,36 +2268,16 @@ static int gather_conv_impl(const float *in, int num_in_rows, const int32_t *nbr
     SG_REQUIRE(ksplit == 1 || a.done != nullptr, "sg_unet_forward(bf16 rows): an offset-split layer needs the in-launch combine");
   }
   if (split) {
-    const int rc = launch_persistent_split(a, num_tiles, in_bytes_ll, w_bytes_ll, stream, split_on == 2, in16 != 0);
+    const int rc = launch_persistent_split(a, d, stream, split_on == 2, in16 != 0);
     if (rc != SG_OK) return rc;
     if (t_chain.mode == 2 && t_chain.args.n > 0) return SG_OK;      // recorded (an offset-split layer combines in the launch)
   } else if (persistent) {
-    // fp32-MFMA kernel (SG_CONV_SPLIT=0 / sg_spconv_set_arithmetic(0), and layers below
-    // SG_CONV_SPLIT_MIN_CIN): 16-channel slices, 2-deep operand ring, 4 waves per unit, one column
-    // block; as many workgroups as are resident at once (a multiple of 8 so that unit u always runs
-    // on XCD u % 8).  (Rounds 1-3 also carried 4- and 8-deep rings, an 80-VGPR build and 64-column
-    // units of this kernel; none of them was faster and they are gone.)
-    const size_t lds = static_cast<size_t>(kWavesPerWg) * 16 * 64 * sizeof(float) +
-                       2 * kMetaInts * sizeof(int32_t) + 16;
-    constexpr int kSliceCh = 16;
-    static int num_cu = 0, occ = 0;
-    static std::once_flag once;
-    std::call_once(once, [&] {
-      int dev = 0;
-      hipGetDevice(&dev);
-      hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev);
-      if (num_cu <= 0) num_cu = 256;
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, gather_conv_persistent_kernel<kSliceCh, 2, 0, 5>, 256, lds);
-      if (occ < 1) occ = 1;
-    });
-    a.magic_nsl = magic(static_cast<unsigned>(Cin / kSliceCh));
+    // fp32-MFMA kernel (see conv_launch_decide)
+    a.magic_nsl = magic(static_cast<unsigned>(Cin / kFp32SliceCh));
     static const bool dyn_env = getenv("SG_CONV_STATIC") && atoi(getenv("SG_CONV_STATIC")) == 0;   // hand-out A/B
     a.queue = dyn_env ? take_tickets(stream) : nullptr;          // (null: static snake, the default)
     a.dyn_rounds = 2;
-    long long g = static_cast<long long>(num_cu) * occ;
-    if (g >= 8) g -= g % 8;
-    if (units < g) g = units >= 8 ? (units + 7) / 8 * 8 : units;      // (see launch_persistent_split)
-    const unsigned ib_ = static_cast<unsigned>(in_bytes_ll), wb_ = static_cast<unsigned>(w_bytes_ll);
+    const unsigned ib_ = static_cast<unsigned>(d.in_bytes), wb_ = static_cast<unsigned>(d.w_bytes);
     static const char *trace_env = getenv("SG_CONV_TRACE");     // developer tool: per-wave phase stamps
     if (trace_env) {
       const size_t nb = static_cast<size_t>(units) * kWavesPerWg * 8 * sizeof(unsigned long long);
@@ -2176,29 +2285,27 @@ static int gather_conv_impl(const float *in, int num_in_rows, const int32_t *nbr
       hipMalloc(&dbuf, nb);
       hipMemsetAsync(dbuf, 0, nb, stream);
       a.trace = dbuf;
-      gather_conv_persistent_kernel<kSliceCh, 2, 1, 5><<<static_cast<int>(g), 256, lds, stream>>>(a, ib_, wb_);
+      gather_conv_persistent_kernel<kFp32SliceCh, 2, 1, 5><<<f.grid, f.block, d.lds, stream>>>(a, ib_, wb_);
       hipStreamSynchronize(stream);
       std::vector<unsigned long long> h(nb / 8);
       hipMemcpy(h.data(), dbuf, nb, hipMemcpyDeviceToHost);
       hipFree(dbuf);
-      if (FILE *f = fopen(trace_env, "ab")) {
-        long long hdr[8] = {M_out, K, Cin, Cout, units, col_units, ksplit, g};
-        fwrite(hdr, 8, 8, f);
-        fwrite(h.data(), 8, h.size(), f);
-        fclose(f);
+      if (FILE *fp = fopen(trace_env, "ab")) {
+        long long hdr[8] = {M_out, K, Cin, Cout, units, f.col_units, ksplit, f.grid};
+        fwrite(hdr, 8, 8, fp);
+        fwrite(h.data(), 8, h.size(), fp);
+        fclose(fp);
       }
     } else {
-      gather_conv_persistent_kernel<kSliceCh, 2, 0, 5><<<static_cast<int>(g), 256, lds, stream>>>(a, ib_, wb_);
+      gather_conv_persistent_kernel<kFp32SliceCh, 2, 0, 5><<<f.grid, f.block, d.lds, stream>>>(a, ib_, wb_);
     }
   } else {
-    const size_t lds = kWavesPerWg * kTileRows * kMaxK * sizeof(int32_t);
-    const int grid = static_cast<int>((units + kWavesPerWg - 1) / kWavesPerWg);
-    const bool vec = (Cin % kCk) == 0;
-    switch (bpu) {
-      case 1: launch_tile<1>(a, grid, lds, vec, stream); break;
-      case 2: launch_tile<2>(a, grid, lds, vec, stream); break;
-      case 3: launch_tile<3>(a, grid, lds, vec, stream); break;
-      default: launch_tile<4>(a, grid, lds, vec, stream); break;
+    const bool vec = f.vec != 0;
+    switch (f.blocks_per_unit) {
+      case 1: launch_tile<1>(a, f.grid, d.lds, vec, stream); break;
+      case 2: launch_tile<2>(a, f.grid, d.lds, vec, stream); break;
+      case 3: launch_tile<3>(a, f.grid, d.lds, vec, stream); break;
+      default: launch_tile<4>(a, f.grid, d.lds, vec, stream); break;
     }
   }
   if (ksplit > 1 && a.done == nullptr) {

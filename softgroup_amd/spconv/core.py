@@ -239,6 +239,30 @@ def gather_conv(features, plan, w_k8, cout, post_scale=None, post_shift=None, re
     return out
 
 
+class ConvLaunchInfo(C.Structure):
+    """sg_conv_launch_info (include/softgroup_hip.h)"""
+    _fields_ = [('family', C.c_int), ('blocks_per_unit', C.c_int), ('vec', C.c_int), ('variant', C.c_int),
+                ('nbw', C.c_int), ('wv', C.c_int), ('ck', C.c_int), ('at', C.c_int), ('ksplit', C.c_int),
+                ('k_per_split', C.c_int), ('combine', C.c_int), ('col_units', C.c_int), ('grid', C.c_int),
+                ('block', C.c_int), ('num_cu', C.c_int), ('occupancy', C.c_int), ('units', C.c_int64)]
+
+
+CONV_FAMILIES = ('scalar', 'tile', 'fp32', 'split', 'bf16')      # sg_conv_launch_info.family
+
+
+def conv_launch_info(num_out, num_in, kvol, cin, cout, have_plan=True, ws_bytes=None, arithmetic=-1):
+    """the launch sg_spconv_gather_conv_f32 would make for such a layer on the current device (nothing is
+    launched); ws_bytes None = the workspace gather_conv passes"""
+    lib = L.lib()
+    if ws_bytes is None:
+        ws_bytes = lib.sg_spconv_conv_workspace_bytes(num_out, cout)
+        ws_bytes = ws_bytes if ws_bytes > 256 else 0
+    info = ConvLaunchInfo()
+    L.check(lib.sg_spconv_conv_launch_info(num_out, num_in, kvol, cin, cout, 1 if have_plan else 0, ws_bytes,
+                                           arithmetic, C.addressof(info)), 'sg_spconv_conv_launch_info')
+    return info
+
+
 def pack_weight_bf16(w, cout, kvol, cin, src_is_kio):
     """fp32 master weight -> the bf16 kernel's packed layout (rounded to nearest even)"""
     lib = L.lib()

@@ -238,6 +238,27 @@ class Reference:
         return min(r['min_ratio'] for r in self.relus.values())
 
 
+class EvalReference(Reference):
+    """the eval-mode forward of the same net (the inference executor's yardstick, tests/test_unet_exec_ref_gpu.py):
+    same tables, same layers and level walk; BatchNorm uses the running statistics with eps, the ReLU is plain (the
+    forward is continuous in its inputs: no ambiguity probe) and there is no backward.  ``forward`` evaluates in
+    `dtype` -- float64 is the reference, float32 the same plain torch ops at the precision of the kernels."""
+
+    def _bn_relu(self, x, name):
+        y = ((x - self.stats[name + '.running_mean']) / torch.sqrt(self.stats[name + '.running_var'] + self.eps)
+             * self.p[name + '.weight'] + self.p[name + '.bias'])
+        return y.clamp(min=0)
+
+    def forward(self, feats, dtype=F64):
+        self.p = {k: v.to(dtype) for k, v in self.sd.items() if v.is_floating_point() and 'running_' not in k}
+        self.stats = {k: v.to(dtype) for k, v in self.sd.items() if 'running_' in k}
+        with torch.no_grad():
+            x = feats.detach().cpu().to(dtype)
+            if 'input_conv.0.weight' in self.p:
+                x = self._conv(x, 'input_conv.0', self.levels[0]['subm'], self.levels[0]['rows'])
+            return self._bn_relu(self._level(x, 0, 'unet.'), 'output_layer.0')
+
+
 def reference_step(state_dict, indices, spatial_shape, batch_size, feats, g_out, **kw):
     run_kw = {k: kw.pop(k) for k in ('input_grad', 'frozen') if k in kw}
     return Reference(state_dict, indices, spatial_shape, batch_size, **kw).run(feats, g_out, **run_kw)
