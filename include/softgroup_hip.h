@@ -1840,6 +1840,51 @@ int sg_grow_segments(const int32_t *nbr, const double *nbr_d2, int64_t n, int k,
                      const float *curvature, double cos_thr, float max_curvature, double max_dist, int min_size,
                      int absorb, int32_t *sp, int32_t *meta, void *ws, size_t ws_bytes, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The object table of a mask list (csrc/objects.hip): per mask its population, axis-aligned box, centroid, centred
+ * second moments, colour mean, the smallest enclosing rectangle over a table of yaw directions and the semantic
+ * vote.  The reference has no counterpart.  Opt-in: nothing calls it unless asked.  softgroup_amd.ops.objects' numpy
+ * twins are the definition; every entry equals them byte for byte, and two calls give the same bytes.  Arithmetic
+ * is integer and IEEE double without contraction; no float atomics.
+ *
+ * INPUTS.  bits uint32 [n, ceil(N / 32)]: point i is bit i % 32 of word i / 32, bits at and beyond N are ignored.
+ * coords float32 [N, 3]; colors float32 [N, 3] or NULL; semantic int32 or int64 [N].  0 <= n <= 16384 masks,
+ * 0 <= N < 2^31 (else SG_ERR_UNSUPPORTED, nothing is launched).  flags int32 [1] is written by the entry: bit
+ * SG_OBJECTS_FLAG_NOT_FINITE when a coordinate (or colour) of a point of at least one mask is not finite -- the
+ * outputs then mean nothing; a value at a point that is in no mask is never read.
+ *
+ * 1. POPULATION AND BOX.  npoint[m] = the number of mask points; aabb[m] = (xmin, ymin, zmin, xmax, ymax, zmax) in
+ *    double from the float32 coordinates.  EVERY extreme of this stage is canonicalised with + 0.0 (-0.0 -> +0.0).
+ * 2. SUMS IN A FIXED ORDER.  The sum over the points of mask m of a double v(i): LEAF of word w: acc = +0.0, then
+ *    acc = acc + v(32 w + b) for the set bits b in ascending order.  TREE: the leaves of words 0 .. W-1, padded with
+ *    +0.0 to the next power of two, are added in adjacent pairs a'[k] = a[2k] + a[2k+1], level by level.  (A leaf is
+ *    never -0.0, so an all-zero subtree may be skipped.)  sum_xyz[m] = the sums of (double)x, (double)y, (double)z;
+ *    centroid = sum / (double)npoint; cov6[m] = the sums of (dx dx, dx dy, dx dz, dy dy, dy dz, dz dz), dx =
+ *    (double)x - cx, each product one multiplication, each sum divided once by (double)npoint; mean_color[m] = the
+ *    three colour sums divided by (double)npoint.
+ * 3. YAW SWEEP.  table double [A, 2] (row_stride 0: one table for all masks) or [n, A, 2] (row_stride A): (c, s)
+ *    per direction, 1 <= A <= 180.  Per mask point u = (double)x * c + (double)y * s, v = (double)y * c - (double)x
+ *    * s (two products and one add or subtract each).  Per (mask, direction) umin, umax, vmin, vmax, each + 0.0;
+ *    area = (umax - umin) * (vmax - vmin).  best_index[m] = the direction of the smallest area, the lowest index
+ *    among equal areas; best_ext[m] = its (umin, umax, vmin, vmax).  all_ext double [n, A, 4], when not NULL, gets
+ *    the four extremes of every direction (then the workspace is not used).
+ * 6. SEMANTIC VOTE.  hist int32 [n, C], 1 <= C <= 256 (else SG_ERR_UNSUPPORTED): per mask the count of every label
+ *    in 0 .. C-1 over its points, other values are not counted.  sem_label[m] = the class of the greatest count, the
+ *    lowest among equal counts, sem_count[m] that count; -1 / 0 for a mask without a counted label.
+ * 7. EMPTY MASKS.  npoint 0, every double output NaN, best_index -1, sem_label -1.
+ * (4. refinement and 5. box composition are host code over these entries: softgroup_amd.util.objects.) */
+#define SG_OBJECTS_FLAG_NOT_FINITE 1
+size_t sg_instance_moments_workspace_bytes(int n, int64_t n_points);
+int sg_instance_moments(const uint32_t *bits, int n, int64_t n_points, const float *coords, const float *colors,
+                        int32_t *npoint, double *aabb, double *sum_xyz, double *centroid, double *cov6,
+                        double *mean_color, int32_t *flags, void *ws, size_t ws_bytes, sg_stream_t stream);
+size_t sg_instance_extents_workspace_bytes(int n, int n_angles);
+int sg_instance_extents(const uint32_t *bits, int n, int64_t n_points, const float *coords, const double *table,
+                        int row_stride, int n_angles, int32_t *best_index, double *best_ext, double *all_ext,
+                        int32_t *flags, void *ws, size_t ws_bytes, sg_stream_t stream);
+int sg_instance_class_hist(const uint32_t *bits, int n, int64_t n_points, const void *semantic, int is_i64,
+                           int n_classes, int32_t *hist, int32_t *sem_label, int32_t *sem_count, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

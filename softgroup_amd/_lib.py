@@ -234,6 +234,11 @@ SIGNATURES = {
     'sg_point_normals': (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'sg_grow_segments_workspace_bytes': (_sz, [_i64]),
     'sg_grow_segments': (_i, [_vp, _vp, _i64, _i, _vp, _vp, _d, _f, _d, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'sg_instance_moments_workspace_bytes': (_sz, [_i, _i64]),
+    'sg_instance_moments': (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_instance_extents_workspace_bytes': (_sz, [_i, _i]),
+    'sg_instance_extents': (_i, [_vp, _i, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_instance_class_hist': (_i, [_vp, _i, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -43,6 +43,7 @@ SOURCES = [
     ('geometry.hip', ['-ffp-contract=off']),
     ('stitch.hip', ['-ffp-contract=off']),
     ('ensemble.hip', ['-ffp-contract=off']),
+    ('objects.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('optim.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),
