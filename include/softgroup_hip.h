@@ -488,6 +488,25 @@ int sg_spconv_gather_conv_bf16(const uint16_t *in, int num_in_rows, const int32_
                                const int32_t *order, const uint32_t *tile_mask, const int32_t *nbr_tiles,
                                uint16_t *out, void *ws, size_t ws_bytes, sg_stream_t stream);
 
+/* Which launch sg_spconv_gather_conv_bf16 would make for a layer of these sizes: the entry point's own
+ * decision (it consumes the same record), a pure function of its arguments -- nothing is launched and no
+ * device is touched.  ws_bytes: as passed to the conv call (0 = no workspace; a workspace too small for
+ * the split forces ksplit = 1).  Meant for tests, which assert through it the form a case reaches.
+ *   col_units, blocks_per_unit: units along cout, 32-column blocks per unit (1..4: the kernel instantiation)
+ *   vec: 16-byte gathers (cin % 16 == 0) or element loads
+ *   ksplit, k_per_split: slices of the kernel-offset range (1 = none), offsets per slice
+ *   num_tiles, units, grid, block: 32-row tiles, waves of work, workgroups, threads each
+ *   ws_used: bytes of the workspace the launch writes (0 when ksplit == 1) */
+typedef struct sg_conv_bf16_launch_info {
+  int col_units, blocks_per_unit, vec;
+  int ksplit, k_per_split;
+  int num_tiles, grid, block;
+  int64_t units;
+  int64_t ws_used;
+} sg_conv_bf16_launch_info;
+int sg_spconv_conv_bf16_launch_info(int num_out_rows, int kvol, int cin, int cout, size_t ws_bytes,
+                                    sg_conv_bf16_launch_info *info);
+
 /* Weight gradient: dw_kio[k][ci][co] = sum_j in[nbr[j,k]][ci] * g_out[j][co]  ([K][Cin][Cout] fp32,
  * overwritten).  in / g_out are fp32, or bf16 when the matching flag is set (widened on load; products
  * and sums are fp32).  Row chunks are accumulated separately and added in chunk order: the result is
@@ -500,6 +519,19 @@ size_t sg_spconv_wgrad_workspace_bytes(int num_out_rows, int kvol, int cin, int 
 int sg_spconv_wgrad(const void *in, int in_is_bf16, const void *g_out, int g_is_bf16, const int32_t *nbr_t,
                     int num_out_rows, int kvol, int cin, int cout, float *dw_kio, void *ws,
                     size_t ws_bytes, sg_stream_t stream);
+
+/* The decomposition sg_spconv_wgrad (and its workspace query) would use for such a layer; a pure function
+ * of the shape, nothing is launched and no device is touched.
+ *   vi, vo: input / gradient channels per lane (1 | 2: the kernel instantiation)
+ *   nst, zs: 32 vi x 32 vo supertiles of the (cin, cout) range, workgroups along z that share them
+ *   rows, chunks: rows per chunk, chunks
+ *   csplit: pieces the centre offset's chunks are cut into (1 = none)
+ *   rs: row split inside a workgroup (4 | 2: the waves' accumulators meet in LDS; 1: whole supertiles per wave) */
+typedef struct sg_wgrad_launch_info {
+  int vi, vo, nst, zs;
+  int rows, chunks, csplit, rs;
+} sg_wgrad_launch_info;
+int sg_spconv_wgrad_launch_info(int num_out_rows, int kvol, int cin, int cout, sg_wgrad_launch_info *info);
 
 /* ------------------------------------------------------------------------------------------
  * Native executor of the sparse U-Net (inference): the whole of

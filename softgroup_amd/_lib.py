@@ -95,6 +95,8 @@ SIGNATURES = {
     'sg_spconv_conv_bf16_workspace_bytes': (_sz, [_i, _i]),
     'sg_spconv_gather_conv_bf16': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                         _vp]),
+    'sg_spconv_conv_bf16_launch_info': (_i, [_i, _i, _i, _i, _sz, _vp]),
+    'sg_spconv_wgrad_launch_info': (_i, [_i, _i, _i, _i, _vp]),
     'sg_spconv_transpose_table': (_i, [_vp, _i, _i, _vp, _vp]),
     'sg_spconv_wgrad_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'sg_spconv_wgrad': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

@@ -257,6 +257,38 @@ static void launch_bf16(const Bf16Args &a, int grid, size_t lds, bool vec, hipSt
   else gather_conv_bf16_kernel<NBW, false><<<grid, 256, lds, stream>>>(a);
 }
 
+// The launch of sg_spconv_gather_conv_bf16 as a pure function of the shape and the workspace on offer: the entry
+// point consumes this record, sg_spconv_conv_bf16_launch_info reports it.  ws_bytes = 0: no workspace.
+static sg_conv_bf16_launch_info conv_bf16_decide(int M_out, int K, int Cin, int Cout, size_t ws_bytes) {
+  sg_conv_bf16_launch_info d;
+  const int NB = (Cout + 31) / 32;
+  const int num_tiles = (M_out + kTRows - 1) / kTRows;
+  // column blocks per unit: as even as possible, at most 4 (64 accumulator registers)
+  const int col_units = (NB + 3) / 4;
+  const int bpu = (NB + col_units - 1) / col_units;
+  int ksplit = 1;
+  const long long waves = static_cast<long long>(num_tiles) * col_units;
+  if (waves < 1024) {
+    const long long want = (1024 + waves - 1) / waves;
+    ksplit = static_cast<int>(want < K ? want : K);
+    const size_t need = static_cast<size_t>(ksplit) * M_out * Cout * sizeof(float);
+    if (ksplit > 1 && ws_bytes < need) ksplit = 1;
+  }
+  const int k_per_split = (K + ksplit - 1) / ksplit;
+  ksplit = (K + k_per_split - 1) / k_per_split;
+  d.col_units = col_units;
+  d.blocks_per_unit = bpu;
+  d.vec = Cin % 16 == 0 ? 1 : 0;
+  d.ksplit = ksplit;
+  d.k_per_split = k_per_split;
+  d.num_tiles = num_tiles;
+  d.units = static_cast<long long>(num_tiles) * col_units * ksplit;
+  d.grid = static_cast<int>((d.units + 3) / 4);
+  d.block = 256;
+  d.ws_used = ksplit > 1 ? static_cast<int64_t>(ksplit) * M_out * Cout * static_cast<int64_t>(sizeof(float)) : 0;
+  return d;
+}
+
 // ---------------------------------------------------------------------------------------------
 // weight gradient
 // ---------------------------------------------------------------------------------------------
@@ -319,6 +351,8 @@ struct RowVec<uint16_t, 2> {
 #define SG_WGRAD_DEPTH 2
 #endif
 constexpr int kWgDepth = SG_WGRAD_DEPTH;      // trips of 8 rows whose loads are in flight per wave
+// row split of a workgroup with `nst` supertiles: 4 / RS waves share the supertiles (sg_spconv_wgrad_launch_info reports it)
+__host__ __device__ constexpr int wgrad_row_split(int nst) { return nst >= 3 ? 1 : (nst == 2 ? 2 : 4); }
 template <typename TA, typename TG, int VI, int VO>
 __global__ void __launch_bounds__(256) conv_wgrad_kernel(const TA *__restrict__ in, const TG *__restrict__ g_out,
                                                         const int32_t *__restrict__ nbr_t, int M_out, int K,
@@ -395,7 +429,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(const TA *__restrict__ 
   const int col = lane & 31, half = lane >> 5;
   const int nsi = (Cin + 32 * VI - 1) / (32 * VI), nso = (Cout + 32 * VO - 1) / (32 * VO);
   const int nst = nsi * nso;
-  const int RS = nst >= 3 ? 1 : (nst == 2 ? 2 : 4);     // row split; 4 / RS waves share the supertiles
+  const int RS = wgrad_row_split(nst);     // row split; 4 / RS waves share the supertiles
   const int ST = 4 / RS;
   const int sw = wave % ST, rs = wave / ST;
   int per = (total + RS - 1) / RS;
@@ -662,21 +696,8 @@ int sg_spconv_gather_conv_bf16(const uint16_t *in, int num_in_rows, const int32_
              "sg_spconv_gather_conv_bf16: input (%lld B) or weights (%lld B) exceed the 2 GiB buffer range",
              in_bytes, w_bytes);
   hipStream_t stream = as_stream(stream_);
-  const int NB = (Cout + 31) / 32;
-  const int num_tiles = (M_out + kTRows - 1) / kTRows;
-  // column blocks per unit: as even as possible, at most 4 (64 accumulator registers)
-  const int col_units = (NB + 3) / 4;
-  const int bpu = (NB + col_units - 1) / col_units;
-  int ksplit = 1;
-  const long long waves = static_cast<long long>(num_tiles) * col_units;
-  if (waves < 1024) {
-    const long long want = (1024 + waves - 1) / waves;
-    ksplit = static_cast<int>(want < K ? want : K);
-    const size_t need = static_cast<size_t>(ksplit) * M_out * Cout * sizeof(float);
-    if (ksplit > 1 && (ws == nullptr || ws_bytes < need)) ksplit = 1;
-  }
-  const int k_per_split = (K + ksplit - 1) / ksplit;
-  ksplit = (K + k_per_split - 1) / k_per_split;
+  const sg_conv_bf16_launch_info d = conv_bf16_decide(M_out, K, Cin, Cout, ws ? ws_bytes : 0);
+  const int col_units = d.col_units, bpu = d.blocks_per_unit, ksplit = d.ksplit, k_per_split = d.k_per_split;
 
   Bf16Args a;
   a.in = in; a.nbr = nbr; a.w = w_k8; a.order = order; a.tile_mask = tile_mask; a.nbr_tiles = nbr_tiles;
@@ -685,10 +706,9 @@ int sg_spconv_gather_conv_bf16(const uint16_t *in, int num_in_rows, const int32_
   a.col_units = col_units; a.blocks_per_unit = bpu; a.ksplit = ksplit; a.k_per_split = k_per_split;
   a.in_bytes = static_cast<unsigned>(in_bytes);
   a.w_bytes = static_cast<unsigned>(w_bytes);
-  const long long units = static_cast<long long>(num_tiles) * col_units * ksplit;
-  const int grid = static_cast<int>((units + 3) / 4);
+  const int grid = d.grid;
   const size_t lds = 4 * kTRows * kTMaxK * sizeof(int32_t);
-  const bool vec = Cin % 16 == 0;
+  const bool vec = d.vec != 0;
   switch (bpu) {
     case 1: launch_bf16<1>(a, grid, lds, vec, stream); break;
     case 2: launch_bf16<2>(a, grid, lds, vec, stream); break;
@@ -702,6 +722,14 @@ int sg_spconv_gather_conv_bf16(const uint16_t *in, int num_in_rows, const int32_
   return check_launch("sg_spconv_gather_conv_bf16");
 }
 
+int sg_spconv_conv_bf16_launch_info(int M_out, int K, int Cin, int Cout, size_t ws_bytes,
+                                    sg_conv_bf16_launch_info *info) {
+  SG_REQUIRE(info != nullptr && M_out >= 1 && K >= 1 && K <= kTMaxK && Cin >= 1 && Cout >= 1,
+             "sg_spconv_conv_bf16_launch_info: bad arguments (M_out=%d K=%d Cin=%d Cout=%d)", M_out, K, Cin, Cout);
+  *info = conv_bf16_decide(M_out, K, Cin, Cout, ws_bytes);
+  return SG_OK;
+}
+
 int sg_spconv_transpose_table(const int32_t *nbr, int M, int K, int32_t *nbr_t, sg_stream_t stream) {
   SG_REQUIRE(M >= 0 && K >= 1 && K <= kTMaxK, "sg_spconv_transpose_table: bad arguments");
   if (M == 0) return SG_OK;
@@ -713,6 +741,16 @@ size_t sg_spconv_wgrad_workspace_bytes(int M_out, int K, int Cin, int Cout) {
   if (M_out <= 0 || K <= 0 || Cin <= 0 || Cout <= 0) return 256;
   const WgradShape w = wgrad_shape(M_out, K, Cin, Cout);
   return static_cast<size_t>(w.chunks) * w.csplit * K * Cin * Cout * sizeof(float) + 256;
+}
+
+int sg_spconv_wgrad_launch_info(int M_out, int K, int Cin, int Cout, sg_wgrad_launch_info *info) {
+  SG_REQUIRE(info != nullptr && M_out >= 1 && K >= 1 && K <= kTMaxK && Cin >= 1 && Cout >= 1,
+             "sg_spconv_wgrad_launch_info: bad arguments (M_out=%d K=%d Cin=%d Cout=%d)", M_out, K, Cin, Cout);
+  const WgradShape w = wgrad_shape(M_out, K, Cin, Cout);
+  info->vi = w.vi; info->vo = w.vo; info->nst = w.nst; info->zs = w.zs;
+  info->rows = w.rows; info->chunks = w.chunks; info->csplit = w.csplit;
+  info->rs = wgrad_row_split(w.nst);
+  return SG_OK;
 }
 
 // dw_kio [K][Cin][Cout] fp32 is overwritten.  `in` is the input the forward conv gathered from

@@ -290,6 +290,40 @@ def gather_conv_bf16(features, plan, w_k8, cout):
     return out
 
 
+class ConvBf16LaunchInfo(C.Structure):
+    """sg_conv_bf16_launch_info (include/softgroup_hip.h)"""
+    _fields_ = [('col_units', C.c_int), ('blocks_per_unit', C.c_int), ('vec', C.c_int), ('ksplit', C.c_int),
+                ('k_per_split', C.c_int), ('num_tiles', C.c_int), ('grid', C.c_int), ('block', C.c_int),
+                ('units', C.c_int64), ('ws_used', C.c_int64)]
+
+
+class WgradLaunchInfo(C.Structure):
+    """sg_wgrad_launch_info (include/softgroup_hip.h)"""
+    _fields_ = [('vi', C.c_int), ('vo', C.c_int), ('nst', C.c_int), ('zs', C.c_int), ('rows', C.c_int),
+                ('chunks', C.c_int), ('csplit', C.c_int), ('rs', C.c_int)]
+
+
+def conv_bf16_launch_info(num_out, kvol, cin, cout, ws_bytes=None):
+    """the launch sg_spconv_gather_conv_bf16 would make (nothing is launched, no device is needed);
+    ws_bytes None = the workspace gather_conv_bf16 passes"""
+    lib = L.lib()
+    if ws_bytes is None:
+        ws_bytes = lib.sg_spconv_conv_bf16_workspace_bytes(num_out, cout)
+        ws_bytes = ws_bytes if ws_bytes > 256 else 0
+    info = ConvBf16LaunchInfo()
+    L.check(lib.sg_spconv_conv_bf16_launch_info(num_out, kvol, cin, cout, ws_bytes, C.addressof(info)),
+            'sg_spconv_conv_bf16_launch_info')
+    return info
+
+
+def wgrad_launch_info(num_out, kvol, cin, cout):
+    """the decomposition sg_spconv_wgrad would use (nothing is launched, no device is needed)"""
+    info = WgradLaunchInfo()
+    L.check(L.lib().sg_spconv_wgrad_launch_info(num_out, kvol, cin, cout, C.addressof(info)),
+            'sg_spconv_wgrad_launch_info')
+    return info
+
+
 def conv_wgrad(feats, g, plan, cin, cout):
     """dW [K, Cin, Cout] fp32 = sum_j feats[nbr[j,k]]^T g[j]; feats / g fp32 or bf16.
     Deterministic (fixed-order chunk sums)."""

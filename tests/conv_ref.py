@@ -17,6 +17,11 @@ Besides the outputs ``layer`` returns what a rounding-error bound needs, per out
 unit roundoff u = 2^-24 any fp32 evaluation, in any summation order, stays within (n + ops) u S of the exact
 value, where ``ops`` counts the epilogue's own roundings (``Layer.ops_out`` / ``ops_act``: one for the
 residual add, two for each scale-and-shift).
+
+For the training kernels (csrc/spconv_train.hip): ``round_bf16`` puts a float64 tensor on the bf16 grid with ONE
+rounding (the kernel rounds an fp32 sum once; double -> float -> bf16 would round twice next to a midpoint),
+``wgrad`` is the weight gradient dW[k] = X_k^T G and ``input_grad`` the scatter form of the layer's transpose,
+each with its S_abs and its product counts.
 """
 import os
 import sys
@@ -112,3 +117,91 @@ def dense_loop(x, w, table):
             if table[j, k] >= 0:
                 out[j] += w[:, k, :].astype(np.float64) @ x[table[j, k]].astype(np.float64)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# the training side: bf16 grid, weight gradient, input gradient
+# ---------------------------------------------------------------------------------------------------
+BF16_MAX = (2.0 - 2.0 ** -7) * 2.0 ** 127
+
+
+def round_bf16(x):
+    """float64 -> nearest bf16 value (ties to even), as float64, rounded ONCE and in float64: x = m 2^e with
+    0.5 <= |m| < 1 (frexp), the 8 significant bits of bf16 are round(m 2^8), scaled back by ldexp.  Below the
+    smallest normal (2^-126) the grid has the fixed spacing 2^-133; above the largest finite value the result
+    is +-inf, as in the float32 -> bf16 conversion; inf and NaN pass through."""
+    x = x.to(F64)
+    m, e = torch.frexp(x)
+    e = e.long().clamp(-200, 200)                     # (beyond: 0 or inf either way; keeps 2^k a normal double)
+    lift = (-125 - e).clamp(min=0)                    # subnormal range: fewer than 8 bits are left
+    q = torch.round(_ldexp(torch.where(x.abs() < 2.0 ** -150, torch.zeros_like(x), m), 8 - lift))
+    r = torch.copysign(_ldexp(q, e + lift - 8), x)    # (a zero keeps the sign of x)
+    r = torch.where(r.abs() > BF16_MAX, torch.copysign(torch.full_like(r, float('inf')), x), r)
+    return torch.where(torch.isfinite(x), r, x)
+
+
+def _ldexp(v, k):
+    """v 2^k, exact: 2^k is put together from its bits (torch.ldexp multiplies by pow(2, k), which a device's
+    pow need not return exactly)"""
+    return v * ((k + 1023) << 52).view(F64)
+
+
+def _table(table, dev):
+    return torch.as_tensor(np.ascontiguousarray(table) if isinstance(table, np.ndarray) else table).to(dev).long()
+
+
+def wgrad(x, g, table):
+    """dW[k] = X_k^T G over the existing (row, offset) pairs: x [N_in, Cin], g [M_out, Cout], table [M_out, K]
+    -> (dW [K, Cin, Cout] float64, S_abs [K, Cin, Cout] = |X_k|^T |G|, n [K] = pairs of offset k)"""
+    table = _table(table, x.device)
+    assert table.ndim == 2 and table.shape[0] == g.shape[0] and int(table.max()) < x.shape[0]
+    x, g = x.to(F64), g.to(F64)
+    K = table.shape[1]
+    dw = x.new_zeros((K, x.shape[1], g.shape[1]))
+    s = torch.zeros_like(dw)
+    n = torch.zeros(K, dtype=torch.long, device=x.device)
+    for k in range(K):
+        j = torch.nonzero(table[:, k] >= 0)[:, 0]
+        xk, gk = x[table[j, k]], g[j]
+        dw[k] = xk.t() @ gk
+        s[k] = xk.abs().t() @ gk.abs()
+        n[k] = j.numel()
+    return dw, s, n
+
+
+def input_grad(g, w, table, n_in):
+    """the layer's transpose as a scatter: dX[table[j, k]] += g[j] @ w[:, k, :]; g [M_out, Cout], w [Cout, K, Cin]
+    -> (dX [n_in, Cin] float64, S_abs [n_in, Cin], n [n_in] = products of one element of that row: pairs x Cout)"""
+    table = _table(table, g.device)
+    assert table.ndim == 2 and table.shape[0] == g.shape[0] and table.shape[1] == w.shape[1] and w.shape[0] == g.shape[1]
+    g, w = g.to(F64), w.to(F64)
+    dx = g.new_zeros((n_in, w.shape[2]))
+    s = torch.zeros_like(dx)
+    n = torch.zeros(n_in, dtype=torch.long, device=g.device)
+    for k in range(table.shape[1]):
+        j = torch.nonzero(table[:, k] >= 0)[:, 0]
+        dst = table[j, k]
+        dx.index_add_(0, dst, g[j] @ w[:, k, :])
+        s.index_add_(0, dst, g[j].abs() @ w[:, k, :].abs())
+        n.index_add_(0, dst, torch.full_like(dst, w.shape[0]))
+    return dx, s, n
+
+
+def wgrad_loop(x, g, table):
+    """wgrad as the plain triple loop (numpy float64; small inputs only)"""
+    dw = np.zeros((table.shape[1], x.shape[1], g.shape[1]))
+    for j in range(table.shape[0]):
+        for k in range(table.shape[1]):
+            if table[j, k] >= 0:
+                dw[k] += np.outer(x[table[j, k]].astype(np.float64), g[j].astype(np.float64))
+    return dw
+
+
+def input_grad_loop(g, w, table, n_in):
+    """input_grad as the plain triple loop (numpy float64; small inputs only)"""
+    dx = np.zeros((n_in, w.shape[2]))
+    for j in range(table.shape[0]):
+        for k in range(table.shape[1]):
+            if table[j, k] >= 0:
+                dx[table[j, k]] += g[j].astype(np.float64) @ w[:, k, :].astype(np.float64)
+    return dx

@@ -24,6 +24,7 @@ def _mirrors():
     from softgroup_amd.spconv import core as SC
     return {
         'sg_conv_launch_info': SC.ConvLaunchInfo,
+        'sg_conv_bf16_launch_info': SC.ConvBf16LaunchInfo, 'sg_wgrad_launch_info': SC.WgradLaunchInfo,
         'sg_unet_block': UE._Block, 'sg_unet_level': UE._Level, 'sg_unet_desc': UE._Desc,
         'sg_train_bn': UT._TBn, 'sg_train_conv': UT._TConv, 'sg_unet_train_block': UT._TBlock,
         'sg_unet_train_level': UT._TLevel, 'sg_unet_train_desc': UT._TDesc,
