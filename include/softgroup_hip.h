@@ -1389,6 +1389,43 @@ int sg_parse_mask_text(const uint8_t *text, int64_t nbytes, uint8_t *flags, uint
                        sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Raw point-cloud text (csrc/cloud_io.hip, csrc/decimal.h): a delimited table of decimal numbers -> float64,
+ * what the reference's preparations read with pandas.read_csv (dataset/s3dis/prepare_data_inst.py:65,84,
+ * dataset/stpls3d/prepare_data_inst_instance_stpls3d.py:39,77) and the vertex lines of an ASCII PLY.
+ * Numbers: [+-]? (D+ ('.' D*)? | '.' D+) ([eE] [+-]? D+)?, converted to the nearest double, ties to even -- what
+ * Python's float() returns, bit for bit -- when the digits without leading zeros are at most 19 and the decimal
+ * exponent of that integer lies in -27..27 (any zero with at most 4 exponent digits is a signed zero).  DECLINED,
+ * never converted wrong: longer digit strings, exponents outside, [+-]? (inf | infinity | nan) in any case.
+ * Malformed: every other token, and tokens above 64 bytes.
+ *
+ * Host entry over n tokens text[begin[k] .. begin[k] + len[k]): value[k] for status 0 (untouched otherwise),
+ * status[k] = 0 ok | 1 declined | 2 malformed.  All pointers are host pointers. */
+int sg_decimal_to_double_host(const uint8_t *text, const int64_t *begin, const int32_t *len, int64_t n, double *value,
+                              uint8_t *status);
+/* Lines end with '\n' (the last one may be missing; "\r\n" is accepted: '\r' is a blank like space and tab).  A
+ * line of blanks alone, and with comment >= 0 a line whose first byte that is no blank equals `comment`, is no
+ * row; the rows are the other lines behind the first skip_lines physical lines.  nbytes < 2^31 (scan values and
+ * offsets are int32).  ws: sg_text_table_workspace_bytes(nbytes) for both calls.  Nothing synchronises.
+ * meta (device int64 [8]), written by both calls: [0] physical lines, [1] rows, [2] byte offset where the data
+ * begins (nbytes when there are not that many lines); sg_text_table_parse adds [3] rows with a declined field,
+ * [4] malformed rows, [5] the lowest 1-based physical line of a malformed row (INT64_MAX: none), [6] 1 when [1]
+ * differs from the `rows` passed. */
+size_t sg_text_table_workspace_bytes(int64_t nbytes);
+int sg_text_table_count(const uint8_t *text, int64_t nbytes, int64_t skip_lines, int comment, int64_t *meta, void *ws,
+                        size_t ws_bytes, sg_stream_t stream);
+/* values float64 [rows, cols] row-major, 1 <= cols <= 64; row_status uint8 [rows]: bit 0 = at least one field
+ * declined (its value slot is left untouched, the row's other fields are valid), bit 1 = malformed (a field
+ * count other than cols, a malformed token, an empty field under a character delimiter, a byte outside
+ * printable ASCII, tab and '\r'; the row's value slots are undefined); row_line int32 [rows]: the 1-based
+ * physical line of every row.  delimiter < 0: fields are separated by runs of blanks, blanks at either end of
+ * a line are ignored.  delimiter = c (printable, no blank): exactly one c between two fields, blanks around a
+ * field are ignored, a c in front of the line's end is an empty field.  With meta[6] set (the text holds more
+ * or fewer rows than `rows`) the first min(rows, meta[1]) rows are written and nothing beyond the arrays. */
+int sg_text_table_parse(const uint8_t *text, int64_t nbytes, int64_t skip_lines, int comment, int delimiter, int cols,
+                        int64_t rows, double *values, uint8_t *row_status, int32_t *row_line, int64_t *meta, void *ws,
+                        size_t ws_bytes, sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Point-cloud pictures of a test run (the reference's tools/visualization.py: get_coords_color :141-231 and
  * write_ply :234-260), csrc/viz_io.hip.  Labels, colours and the PLY's vertex text are produced in device
  * memory; the caller reads the files, moves the text to pinned memory and writes it.  Nothing synchronises.

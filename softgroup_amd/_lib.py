@@ -178,7 +178,11 @@ SIGNATURES = {
     'sg_parse_decimal_lines_workspace_bytes': (_sz, [_i64]),
     'sg_parse_decimal_lines': (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     'sg_parse_mask_text': (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
-    'sg_viz_paint_bits': (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'sg_decimal_to_double_host': (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    'sg_text_table_workspace_bytes': (_sz, [_i64]),
+    'sg_text_table_count': (_i, [_vp, _i64, _i64, _i, _vp, _vp, _sz, _vp]),
+    'sg_text_table_parse': (_i, [_vp, _i64, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_viz_paint_bits':(_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     'sg_viz_paint_runs_workspace_bytes': (_sz, [_i, _i64]),
     'sg_viz_paint_runs': (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sg_viz_gt_labels': (_i, [_vp, _i64, _vp, _vp, _vp]),

@@ -35,6 +35,7 @@ SOURCES = [
     ('det_eval.hip', ['-ffp-contract=off']),
     ('train_data.hip', ['-ffp-contract=off']),
     ('result_io.hip', ['-ffp-contract=off']),
+    ('cloud_io.hip', ['-ffp-contract=off']),
     ('viz_io.hip', ['-ffp-contract=off']),
     ('mask_nms.hip', ['-ffp-contract=off']),
     ('mask_split.hip', ['-ffp-contract=off']),

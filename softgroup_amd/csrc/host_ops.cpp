@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/softgroup_hip.h"
+#include "decimal.h"
 
 namespace sg {
 void set_error(const char *fmt, ...);
@@ -365,6 +366,24 @@ int sg_host_colmax_i64(const int64_t *src, int64_t rows, int64_t cols, int64_t *
       }
   }
   for (int64_t c = 0; c < cols; ++c) out_max[c] = m[c];
+  return SG_OK;
+}
+
+// decimal.h's routine over n tokens text[begin[k] .. begin[k] + len[k]): value[k] for status 0 (untouched
+// otherwise), status[k] = 0 ok | 1 declined | 2 malformed.  The device readers (cloud_io.hip) call the same code.
+int sg_decimal_to_double_host(const uint8_t *text, const int64_t *begin, const int32_t *len, int64_t n, double *value,
+                              uint8_t *status) {
+  if (n < 0 || (n > 0 && (text == nullptr || begin == nullptr || len == nullptr || value == nullptr ||
+                          status == nullptr))) {
+    sg::set_error("sg_decimal_to_double_host: bad arguments");
+    return SG_ERR_ARG;
+  }
+  for (int64_t k = 0; k < n; ++k) {
+    double v = 0.0;
+    const int st = len[k] < 0 ? sg::kDecimalMalformed : sg::decimal_to_double(text + begin[k], len[k], &v);
+    if (st == sg::kDecimalOk) value[k] = v;
+    status[k] = static_cast<uint8_t>(st);
+  }
   return SG_OK;
 }
 
