@@ -1954,6 +1954,66 @@ int sg_instance_extents(const uint32_t *bits, int n, int64_t n_points, const flo
 int sg_instance_class_hist(const uint32_t *bits, int n, int64_t n_points, const void *semantic, int is_i64,
                            int n_classes, int32_t *hist, int32_t *sem_label, int32_t *sem_count, sg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Result clouds to images (csrc/render.hip): a z-buffered point splat over several views at once and the colour
+ * lookup with optional eye-dome lighting.  The reference has no counterpart.  Opt-in: nothing calls it unless asked.
+ * softgroup_amd.ops.render's numpy twins are the definition; both entries equal them byte for byte, and two calls
+ * give the same bytes: a z-buffer is a minimum over integer keys, so the order of arrival does not matter.  No float
+ * atomics; every operation below is ONE IEEE double operation, in the order written, without contraction; the device
+ * evaluates no transcendental function.
+ *
+ * INPUTS.  coords float32 [N, 3].  cams double [V, SG_RENDER_CAMERA_DOUBLES], in device memory, one row per view:
+ * [0] kind (0 perspective, 1 orthographic), [1..3] eye, [4..12] the rotation row-major with rows (right, up,
+ * forward), [13] f, [14] cx, [15] cy, [16] 1 when near is given, [17] near, [18] 1 when far is given, [19] far.
+ * The host computes all of it once, for both backends; a perspective camera needs near > 0.  Image width W, height
+ * H, row 0 at the top.  Either point_size, the splat radius in pixels (0 .. 16), or world_radius w > 0 (then
+ * point_size is ignored).  Range: 0 <= N < 2^31 - 1, 1 <= V <= 16, 1 <= W, H <= 8192, V H W <= 2^26 (else
+ * SG_ERR_UNSUPPORTED, nothing is launched).
+ *
+ * RULES per (view, point i).
+ *   dx = (double)x - ex, dy, dz likewise; xc = (r00 dx + r01 dy) + r02 dz, yc and zc from rows 1 and 2.
+ *   Visible when zc >= near (near given) and zc <= far (far given); a comparison with NaN is false, so a coordinate
+ *   that is not finite culls itself.
+ *   perspective: u = cx + f (xc / zc), v = cy - f (yc / zc); orthographic: u = cx + f xc, v = cy - f yc.
+ *   Culled unless -2^30 < u < 2^30 and -2^30 < v < 2^30, tested on the doubles before any conversion to an integer.
+ *   px = floor(u), py = floor(v).
+ *   r = point_size, or with w: perspective floor(f (w / zc)), orthographic floor(f w), clipped to 0 .. 16.
+ *   The point covers the pixels (px + a, py + b), a, b = -r .. r, that lie inside the image (a splat across a border
+ *   is clipped per pixel, not dropped).
+ *   d = (float)zc + 0.0f; key = (ord32(d) << 32) | i, ord32 the order-preserving map of the float bits (all bits
+ *   flipped for a negative value, the sign bit set otherwise).  The pixel's owner is the smallest key: the nearest
+ *   depth after rounding to float32, the LOWEST point among equal depths.  All ones = empty.
+ * index int32 [V, H, W] gets the owner (-1: empty), depth float32 [V, H, W] its d (+inf: empty), culled int32 [V]
+ * the number of culled points of every view (not an error).  Emptiness is index < 0: a zc beyond the float32 range
+ * rounds to d = +inf and the point still owns its pixel, with depth +inf.
+ *
+ * stages: SG_RENDER_STAGE_ALL, or for measurements the stages one by one on the same workspace, in this order: FILL
+ * (keys [V, H, W] uint64 in the workspace to all ones, culled to 0), SPLAT (a lane per point, the views in an inner
+ * loop; per covered pixel an 8-byte relaxed agent-scope load and a 64-bit atomicMin only when the key is smaller),
+ * RESOLVE (a lane per pixel, keys to index / depth).
+ *
+ * SHADE.  image uint8 [V, H, W, 3]: the background for an empty pixel, colors[i] (uint8 [n_colors, 3]) for a pixel
+ * owned by point i.  An owner outside 0 .. n_colors-1 is never dereferenced: the pixel gets the background and flags
+ * int32 [1] gets SG_RENDER_FLAG_COLOR_INDEX.  With edl != 0 (strength >= 0, radius s in 1 .. 4, scale > 0) every
+ * channel of an owned pixel of depth d is scaled: the eight neighbours at (dx, dy) s, (dx, dy) in the order
+ * (-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (1, -1), (-1, 1), (1, 1) (dy > 0 is down); a neighbour outside the
+ * image is not counted; an empty one contributes 0; any other one t = (double)d - (double)dn, t = t > 0 ? t : 0,
+ * t = t / scale, t = t < 1 ? t : 1.  resp = the sum in that order, from +0.0, divided by (double)count, or 0 when
+ * count == 0; shade = 1.0 / (1.0 + strength resp); c' = (uint8)floor((double)c shade + 0.5). */
+#define SG_RENDER_CAMERA_DOUBLES 20
+#define SG_RENDER_FLAG_COLOR_INDEX 1
+#define SG_RENDER_STAGE_FILL 1
+#define SG_RENDER_STAGE_SPLAT 2
+#define SG_RENDER_STAGE_RESOLVE 4
+#define SG_RENDER_STAGE_ALL 7
+size_t sg_render_rasterize_workspace_bytes(int n_views, int width, int height);
+int sg_render_rasterize(const float *coords, int64_t n, const double *cams, int n_views, int width, int height,
+                        int point_size, double world_radius, int stages, int32_t *index, float *depth,
+                        int32_t *culled, void *ws, size_t ws_bytes, sg_stream_t stream);
+int sg_render_shade(const int32_t *index, const float *depth, int n_views, int width, int height,
+                    const uint8_t *colors, int64_t n_colors, int bg_r, int bg_g, int bg_b, int edl, double strength,
+                    int radius, double scale, uint8_t *image, int32_t *flags, sg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

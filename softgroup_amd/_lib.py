@@ -245,6 +245,9 @@ SIGNATURES = {
     'sg_instance_extents_workspace_bytes': (_sz, [_i, _i]),
     'sg_instance_extents': (_i, [_vp, _i, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sg_instance_class_hist': (_i, [_vp, _i, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'sg_render_rasterize_workspace_bytes': (_sz, [_i, _i, _i]),
+    'sg_render_rasterize': (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_render_shade': (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _i, _i, _i, _i, _d, _i, _d, _vp, _vp, _vp]),
 }
 
 

@@ -45,6 +45,7 @@ SOURCES = [
     ('stitch.hip', ['-ffp-contract=off']),
     ('ensemble.hip', ['-ffp-contract=off']),
     ('objects.hip', ['-ffp-contract=off']),
+    ('render.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('optim.hip', ['-ffp-contract=off']),
     ('host_ops.cpp', ['-ffp-contract=off']),
