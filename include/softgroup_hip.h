@@ -1258,6 +1258,75 @@ int sg_det_match(const double *det_box, const int32_t *det_group, const int32_t 
                  sg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Yaw-oriented 3D boxes against each other (csrc/box_ops.hip): the IoU matrix, eval_det_cls's matching with that IoU
+ * and greedy box NMS.  The reference has no counterpart.  Opt-in: nothing calls it unless asked.
+ * softgroup_amd.ops.boxes.obb_iou_pair is the definition (box_iou_numpy its vectorised twin); every entry equals it
+ * byte for byte, and two calls give the same bytes.  Every operation below is ONE IEEE double operation, in the
+ * association written, without contraction; the device evaluates no transcendental function; no float atomics.
+ *
+ * BOX ROW.  8 doubles (cx, cy, cz, du, dv, dz, c, s): du lies along (c, s), dv along (-s, c), (c, s) = (cos theta, sin
+ * theta) computed once on the host for both backends (softgroup_amd.ops.boxes.boxes8).  A row with an entry that is
+ * not finite or with a negative extent is INVALID: it sets SG_BOX_FLAG_INVALID in the entry's flag word, and the
+ * outputs then mean nothing.  No kernel depends on a box being valid in order to terminate or to stay inside its
+ * arrays: every loop has a constant bound and every polygon store a slot below 8.
+ *
+ * AREA(a, b), rectangle a clipped in b's frame (the arguments are not interchangeable at the last bit).
+ *   1. hua = 0.5 du_a, hva = 0.5 dv_a.
+ *   2. corners k = 0 .. 3, signs (su, sv) = (-,-), (+,-), (+,+), (-,+): u = su hua, v = sv hva,
+ *      x = cx_a + (u c_a - v s_a), y = cy_a + (u s_a + v c_a).
+ *   3. dx = x - cx_b, dy = y - cy_b, p = (dx c_b + dy s_b, dy c_b - dx s_b).
+ *   4. Sutherland-Hodgman against (axis 0, +, hub), (axis 0, -, hub), (axis 1, +, hvb), (axis 1, -, hvb), hub = 0.5
+ *      du_b, hvb = 0.5 dv_b.  For the edges (P[i], P[(i + 1) % n]), i ascending: dp = h - sign p[axis], dq likewise; a
+ *      vertex is inside when d >= 0 (inclusive; a NaN is outside); p is emitted when inside; when exactly one end is
+ *      inside r is emitted as well, t = dp / (dp - dq) (not 0: the signs differ), every coordinate p_k + t (q_k -
+ *      p_k), the clipped coordinate then set to exactly sign h.  An empty polygon ends the walk with area 0.  A
+ *      convex polygon gains at most one vertex per plane, so 8 slots hold it; an emit into a full polygon is dropped
+ *      (never reached by valid boxes).
+ *   5. fewer than 3 vertices: area 0.
+ *   6. S = +0.0; for i = 1 .. n-2 ascending S = S + ((x_i - x0)(y_{i+1} - y0) - (x_{i+1} - x0)(y_i - y0)); area = 0.5
+ *      |S|.
+ * IOU, SG_BOX_IOU_3D.  zlo = max(cz_a - 0.5 dz_a, cz_b - 0.5 dz_b), zhi = min(cz_a + 0.5 dz_a, cz_b + 0.5 dz_b) (max(x,
+ * y) = x > y ? x : y, min(x, y) = x < y ? x : y), h = zhi - zlo; when h > 0 is false the IoU is 0.0, decided before
+ * any clipping.  A = area(a, b); when A > 0 is false the IoU is 0.0.  inter = A h, va = (du_a dv_a) dz_a, vb
+ * likewise, uni = (va + vb) - inter; when uni > 0 is false the IoU is 0.0, else inter / uni.  SG_BOX_IOU_BEV: the same
+ * without z, uni = (du_a dv_a + du_b dv_b) - A.  Not clamped: a box against itself gives 1 within a few ulps.
+ * Touching boxes and boxes of zero extent give exactly 0.  Thresholds compare strictly: iou > thr.
+ *
+ * sg_box_iou: iou[i n_b + j] = iou(a_i, b_j).  RANGE: 0 <= n_a, n_b and n_a n_b <= 2^30, else SG_ERR_UNSUPPORTED,
+ * nothing is launched and nothing truncated.  flags int32 [1] (device, zeroed by the caller) gets
+ * SG_BOX_FLAG_INVALID. */
+#define SG_BOX_IOU_3D 0
+#define SG_BOX_IOU_BEV 1
+#define SG_BOX_FLAG_INVALID 1
+int sg_box_iou(const double *a, int64_t n_a, const double *b, int64_t n_b, int mode, double *iou, int32_t *flags,
+               sg_stream_t stream);
+
+/* sg_det_match with box rows of 8 doubles and the IoU above (mode = SG_BOX_IOU_*): ovmax[d], jmax[d] = the first GT
+ * of detection d's (class, image) group with the strictly largest IoU (-inf / -1 without one); the claims are
+ * resolved by rank and threshold exactly as sg_det_match does.  The host validates the boxes (there is no flag
+ * word).  RANGE: n_det, n_gt < 2^31, 1 <= n_thresholds <= SG_DET_MAX_THRESHOLDS (else SG_ERR_ARG). */
+size_t sg_det_match_obb_workspace_bytes(int64_t n_gt, int n_thresholds);
+int sg_det_match_obb(const double *det_box, const int32_t *det_group, const int32_t *det_rank, int64_t n_det,
+                     const double *gt_box, const int64_t *group_off, int64_t n_gt, const double *thresholds,
+                     int n_thresholds, int mode, double *ovmax, int64_t *jmax, uint8_t *tp, void *ws, size_t ws_bytes,
+                     sg_stream_t stream);
+
+/* Greedy box NMS: the ORDER and the LOOP of sg_mask_nms, read with iou > thr.  boxes: box rows [n]; scores float32
+ * [n], all finite; labels int32 [n], NULL = class-agnostic (as class_agnostic != 0).  Descending score, the LOWER
+ * index first among equal scores (-0.0 equals 0.0); a kept box suppresses every later, not yet suppressed box of its
+ * label with iou > thr; a suppressed box suppresses nobody.  The pair of original indices i < j is evaluated as
+ * iou(box_i, box_j), so the value does not depend on the scores.  keep uint8 [n] (1 = kept) in the original order;
+ * n_keep int32 [2] (device): [0] = their number, [1] = the flag word (SG_BOX_FLAG_INVALID; written by the entry).
+ * iou_out (may be NULL): double [n, n], [i, j] = [j, i] = iou(box_i, box_j) for i <= j, every pair whatever the labels.
+ * RANGE: 0 <= n <= 16384; beyond it the call returns SG_ERR_UNSUPPORTED and sg_box_nms_workspace_bytes returns 0 --
+ * nothing is truncated.  Nothing synchronises, there is no host read-back and no float atomic (the decide matrix is
+ * set by integer atomicOr). */
+size_t sg_box_nms_workspace_bytes(int n);
+int sg_box_nms(const double *boxes, int n, const float *scores, const int32_t *labels, double thr, int mode,
+               int class_agnostic, uint8_t *keep, int32_t *n_keep, double *iou_out, void *ws, size_t ws_bytes,
+               sg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training-time data transform (softgroup/data/custom.py:52-194, data/kitti.py:78-118,
  * data/s3dis.py:31-41).  Points are [n, 3] row-major; labels int64.  `stats` receives 9 uint64
  * order-preserving keys of float64 values -- max |x|, min x, max x per axis -- decoded by the caller

@@ -151,6 +151,11 @@ SIGNATURES = {
     'sg_det_boxes_labels': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     'sg_det_match_workspace_bytes': (_sz, [_i64, _i]),
     'sg_det_match': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_box_iou': (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _vp]),
+    'sg_det_match_obb_workspace_bytes': (_sz, [_i64, _i]),
+    'sg_det_match_obb': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sg_box_nms_workspace_bytes': (_sz, [_i]),
+    'sg_box_nms': (_i, [_vp, _i, _vp, _vp, _d, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sg_bn_relu_f32': (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     'sg_gather_rows_f32': (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     'sg_gather_rows_i64idx_f32': (_i, [_vp, _vp, _i64, _i, _vp, _vp]),

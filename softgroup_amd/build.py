@@ -33,6 +33,7 @@ SOURCES = [
     ('eval_ops.hip', ['-ffp-contract=off']),
     ('inst_eval.hip', ['-ffp-contract=off']),
     ('det_eval.hip', ['-ffp-contract=off']),
+    ('box_ops.hip', ['-ffp-contract=off']),
     ('train_data.hip', ['-ffp-contract=off']),
     ('result_io.hip', ['-ffp-contract=off']),
     ('cloud_io.hip', ['-ffp-contract=off']),

@@ -19,6 +19,7 @@
 //             (readlane, no memory), then the survivors' rows are OR-ed into the `removed` vector in LDS with all
 //             their loads independent -- two memory round trips per 32 masks, not one per mask.
 #include "common.h"
+#include "nms_greedy.h"
 
 namespace sg {
 
@@ -204,6 +205,16 @@ __global__ void __launch_bounds__(kWave) nms_greedy_kernel(const uint32_t *__res
     __syncthreads();
   }
   if (lane == 0) *n_keep = kept_total;
+}
+
+// nms_greedy.h: the same two kernels for the box NMS of box_ops.hip
+void nms_rank_launch(const float *scores, int n, int32_t *rank, int32_t *order, hipStream_t stream) {
+  nms_rank_kernel<<<grid_for(n, kNmsBlock, 1024), kNmsBlock, 0, stream>>>(scores, n, rank, order);
+}
+
+void nms_greedy_launch(const uint32_t *decide, const int32_t *order, int n, int nw, uint8_t *keep, int32_t *n_keep,
+                       hipStream_t stream) {
+  nms_greedy_kernel<<<1, kWave, 0, stream>>>(decide, order, n, nw, keep, n_keep);
 }
 
 }  // namespace sg

@@ -1,4 +1,5 @@
-from .det_eval import eval_det, eval_det_cls, eval_sphere, evaluate_box_ap, get_iou, voc_ap  # noqa: F401
+from .det_eval import (eval_det, eval_det_cls, eval_sphere, evaluate_box_ap, get_iou,  # noqa: F401
+                       get_iou_bev, get_iou_obb, oriented_instance_boxes, voc_ap)
 from .instance_eval import ScanNetEval
 from .panoptic_eval import PanopticEval
 from .point_wise_eval import evaluate_offset_mae, evaluate_semantic_acc, evaluate_semantic_miou

@@ -17,6 +17,13 @@ runs instead: the same IoU operations, vectorised over each detection's GT boxes
 greedy pass.  Quirks are kept: ``eval_det`` raises KeyError for a GT class without predictions, where
 ``eval_sphere`` reports 0; a class with predictions and no GT has npos = 0 and numpy's nan / inf
 recall.
+
+Yaw-oriented boxes (no counterpart in the reference): ``get_iou_obb`` / ``get_iou_bev`` score 7-number
+boxes (cx, cy, cz, du, dv, dz, theta) by the rules of ``softgroup_amd.ops.boxes``; passed as
+``get_iou_func`` they take ``sg_det_match_obb`` on the GPU and a vectorised numpy path without one, both
+equal to the reference loop with the same function.  ``oriented_instance_boxes`` forms such boxes
+through ``describe_instances``, and ``evaluate_box_ap(boxes='obb')`` scores them; with the default
+``boxes='aabb'`` nothing changes.
 """
 import numpy as np
 
@@ -60,6 +67,20 @@ def get_iou(box_a, box_b, eps=1e-10):
     vol_b = (box_b[3:6] - box_b[:3]).prod()
     union = vol_a + vol_b - intersection
     return 1.0 * intersection / union
+
+
+def get_iou_obb(box_a, box_b):
+    """IoU of two yaw-oriented boxes given as (cx cy cz du dv dz theta): the definition of
+    ``softgroup_amd.ops.boxes``.  Usable as the ``get_iou_func`` of eval_det_cls / eval_det /
+    eval_sphere, which then match on the device (or vectorised) when every box has 7 numbers."""
+    from ..ops import boxes as BX
+    return BX.obb_iou_pair(BX.boxes8(box_a)[0], BX.boxes8(box_b)[0], '3d')
+
+
+def get_iou_bev(box_a, box_b):
+    """get_iou_obb in the bird's-eye view: the IoU of the two rectangles in the xy plane."""
+    from ..ops import boxes as BX
+    return BX.obb_iou_pair(BX.boxes8(box_a)[0], BX.boxes8(box_b)[0], 'bev')
 
 
 def _iou_rows(bb, gts):
@@ -110,6 +131,15 @@ class _ClassJob:
             return None
         for s in self.gt_sphere.values():
             if s.size and (s.ndim != 2 or s.shape[1] != 6):
+                return None
+        return True
+
+    def boxes7(self):
+        """True when every detection and GT box has seven numbers (the oriented IoU's fast paths)"""
+        if self.nd and (self.BB.ndim != 2 or self.BB.shape[1] != 7):
+            return None
+        for s in self.gt_sphere.values():
+            if s.size and (s.ndim != 2 or s.shape[1] != 7):
                 return None
         return True
 
@@ -177,9 +207,39 @@ def _match_numpy(job, ovthreshs):
     return [_greedy(ov, jm, img_of, t) for t in ovthreshs]
 
 
-def _match_device(jobs, ovthreshs, device):
-    """TP flags per (job, threshold) in each job's sorted order, for all jobs in one sg_det_match"""
+def _match_numpy_obb(job, ovthreshs, mode):
+    """(ovmax, jmax) with the oriented IoU, one vectorised IoU matrix per image, then the greedy pass"""
+    from ..ops import boxes as BX
+    img_of = [job.image_ids[x] for x in job.sorted_ind]
+    BB = BX.boxes8(job.BB[job.sorted_ind, ...].astype(float)) if job.nd else np.zeros((0, 8))
+    ov = np.full(job.nd, -np.inf)
+    jm = np.full(job.nd, -1, np.int64)
+    rows_of = {}
+    for d, img_id in enumerate(img_of):
+        rows_of.setdefault(img_id, []).append(d)
+    for img_id, rows in rows_of.items():
+        G = job.gt_sphere[img_id].astype(float)
+        if G.size == 0:
+            continue
+        rows = np.asarray(rows)
+        iou = BX.box_iou_numpy(BB[rows], BX.boxes8(G), mode)
+        cand = np.where(np.isnan(iou), -np.inf, iou)       # NaN never wins `iou > ovmax`
+        j = np.argmax(cand, axis=1)                        # the first of the largest
+        best = cand[np.arange(len(rows)), j]
+        hit = best > -np.inf
+        ov[rows[hit]], jm[rows[hit]] = best[hit], j[hit]
+    return [_greedy(ov, jm, img_of, t) for t in ovthreshs]
+
+
+def _match_device(jobs, ovthreshs, device, mode=None):
+    """TP flags per (job, threshold) in each job's sorted order, for all jobs in one sg_det_match
+    (mode None: six-number boxes) or one sg_det_match_obb (mode '3d' / 'bev': seven-number boxes)"""
     import torch
+    if mode is None:
+        width, rows = 6, (lambda b: np.asarray(b, np.float64).reshape(-1, 6))
+    else:
+        from ..ops import boxes as BX
+        width, rows = 8, (lambda b: BX.boxes8(np.asarray(b, np.float64).reshape(-1, 7)))
     dev = torch.device('cuda' if device is None else device)
     det_box, det_group, det_rank, gt_box, group_sizes = [], [], [], [], []
     for job in jobs:
@@ -187,9 +247,9 @@ def _match_device(jobs, ovthreshs, device):
         for img_id, s in job.gt_sphere.items():
             group_sizes.append(len(s) if s.size else 0)
             if s.size:
-                gt_box.append(np.asarray(s, np.float64).reshape(-1, 6))
+                gt_box.append(rows(s))
         if job.nd:
-            det_box.append(np.asarray(job.BB, np.float64).reshape(-1, 6))
+            det_box.append(rows(job.BB))
             det_group.append(np.array([groups[i] for i in job.image_ids], np.int32))
             rank = np.empty(job.nd, np.int32)
             rank[job.sorted_ind] = np.arange(job.nd, dtype=np.int32)
@@ -198,8 +258,8 @@ def _match_device(jobs, ovthreshs, device):
     if n_det == 0:
         return [[np.zeros(0, np.uint8) for _ in ovthreshs] for _ in jobs]
     tp = match_boxes(np.concatenate(det_box), np.concatenate(det_group), np.concatenate(det_rank),
-                     np.concatenate(gt_box) if gt_box else np.zeros((0, 6)), np.asarray(group_sizes, np.int64),
-                     ovthreshs, dev)[2]
+                     np.concatenate(gt_box) if gt_box else np.zeros((0, width)), np.asarray(group_sizes, np.int64),
+                     ovthreshs, dev, mode)[2]
     out, o = [], 0
     for job in jobs:
         out.append([tp[k, o:o + job.nd][job.sorted_ind] for k in range(len(ovthreshs))])
@@ -207,10 +267,18 @@ def _match_device(jobs, ovthreshs, device):
     return out
 
 
-def match_boxes(det_box, det_group, det_rank, gt_box, group_sizes, ovthreshs, device):
+def match_boxes(det_box, det_group, det_rank, gt_box, group_sizes, ovthreshs, device, mode=None):
     """sg_det_match on host arrays -> (ovmax [n_det] fp64, jmax [n_det] global GT row, tp
-    [n_thr, n_det] uint8), numpy arrays"""
+    [n_thr, n_det] uint8), numpy arrays.  With mode '3d' / 'bev' the boxes are box rows of 8 doubles
+    (``softgroup_amd.ops.boxes.boxes8``) and sg_det_match_obb runs; an invalid box raises ValueError."""
     import torch
+    width = 6
+    if mode is not None:
+        from ..ops import boxes as BX
+        BX._mode(mode)
+        width = 8
+        BX._check(BX._rows8(det_box, 'det_box'), 'match_boxes')
+        BX._check(BX._rows8(np.asarray(gt_box, np.float64).reshape(-1, 8), 'gt_box'), 'match_boxes')
     ovthreshs = [float(t) for t in ovthreshs]
     assert 1 <= len(ovthreshs) <= MAX_THRESHOLDS
     n_det, n_gt = len(det_group), len(gt_box)
@@ -218,12 +286,12 @@ def match_boxes(det_box, det_group, det_rank, gt_box, group_sizes, ovthreshs, de
     d_det = torch.from_numpy(np.ascontiguousarray(det_box, np.float64)).to(device)
     d_grp = torch.from_numpy(np.ascontiguousarray(det_group, np.int32)).to(device)
     d_rank = torch.from_numpy(np.ascontiguousarray(det_rank, np.int32)).to(device)
-    d_gt = torch.from_numpy(np.ascontiguousarray(gt_box, np.float64).reshape(-1, 6)).to(device)
+    d_gt = torch.from_numpy(np.ascontiguousarray(gt_box, np.float64).reshape(-1, width)).to(device)
     d_off = torch.from_numpy(off).to(device)
-    return _match_launch(d_det, d_grp, d_rank, n_det, d_gt, d_off, n_gt, ovthreshs)
+    return _match_launch(d_det, d_grp, d_rank, n_det, d_gt, d_off, n_gt, ovthreshs, mode)
 
 
-def _match_launch(d_det, d_grp, d_rank, n_det, d_gt, d_off, n_gt, ovthreshs):
+def _match_launch(d_det, d_grp, d_rank, n_det, d_gt, d_off, n_gt, ovthreshs, mode=None):
     import ctypes
     import torch
     from .. import _lib as L
@@ -232,6 +300,14 @@ def _match_launch(d_det, d_grp, d_rank, n_det, d_gt, d_off, n_gt, ovthreshs):
     ovmax = torch.empty(n_det, dtype=torch.float64, device=dev)
     jmax = torch.empty(n_det, dtype=torch.int64, device=dev)
     tp = torch.empty((len(ovthreshs), n_det), dtype=torch.uint8, device=dev)
+    if mode is not None:
+        from ..ops import boxes as BX
+        ws = L.workspace(L.lib().sg_det_match_obb_workspace_bytes(n_gt, len(ovthreshs)), dev)
+        L.check(L.lib().sg_det_match_obb(L.ptr(d_det), L.ptr(d_grp), L.ptr(d_rank), n_det, L.ptr(d_gt), L.ptr(d_off),
+                                         n_gt, ctypes.cast(th, ctypes.c_void_p), len(ovthreshs), BX._mode(mode),
+                                         L.ptr(ovmax), L.ptr(jmax), L.ptr(tp), L.ptr(ws), ws.numel(), L.stream()),
+                'sg_det_match_obb')
+        return ovmax.cpu().numpy(), jmax.cpu().numpy(), tp.cpu().numpy()
     ws = L.workspace(L.lib().sg_det_match_workspace_bytes(n_gt, len(ovthreshs)), dev)
     L.check(L.lib().sg_det_match(L.ptr(d_det), L.ptr(d_grp), L.ptr(d_rank), n_det, L.ptr(d_gt), L.ptr(d_off), n_gt,
                                  ctypes.cast(th, ctypes.c_void_p), len(ovthreshs), L.ptr(ovmax), L.ptr(jmax),
@@ -241,7 +317,13 @@ def _match_launch(d_det, d_grp, d_rank, n_det, d_gt, d_off, n_gt, ovthreshs):
 
 def _eval_jobs(jobs, ovthreshs, use_07_metric, get_iou_func, device):
     """[(rec, prec, ap) per threshold] per job"""
-    if get_iou_func is not get_iou or any(job.boxes6() is None for job in jobs):
+    obb = '3d' if get_iou_func is get_iou_obb else 'bev' if get_iou_func is get_iou_bev else None
+    if obb is not None and all(job.boxes7() for job in jobs):
+        if use_device(device) and len(ovthreshs) <= MAX_THRESHOLDS:
+            flags = _match_device(jobs, ovthreshs, device, obb)
+        else:
+            flags = [_match_numpy_obb(job, ovthreshs, obb) for job in jobs]
+    elif get_iou_func is not get_iou or any(job.boxes6() is None for job in jobs):
         flags = [_match_reference_loop(job, ovthreshs, get_iou_func) for job in jobs]
     elif use_device(device) and len(ovthreshs) <= MAX_THRESHOLDS:
         flags = _match_device(jobs, ovthreshs, device)
@@ -449,16 +531,63 @@ def instance_boxes(coords, masks, instance_labels, device=None):
     return out, gt
 
 
+def oriented_instance_boxes(coords, masks, instance_labels, yaw_steps=90, refine=0, backend='auto'):
+    """``instance_boxes`` with yaw-oriented boxes: every scan's prediction masks and GT instances go
+    through ``describe_instances`` (the enclosing rectangle of least area over ``yaw_steps`` directions
+    times the z range, float32 coordinates).  The GT owners are ``instance_labels == i`` for i in
+    range(max + 1), as in ``instance_boxes``.
+    -> (per scan obb [n_masks, 7] fp64 = (cx, cy, cz, du, dv, dz, theta), per scan (GT obb [k, 7], point
+    counts [k], first point index [k] (-1: no points))).  A mask without points raises ValueError; an
+    owner without points has a NaN box and count 0, which ``evaluate_box_ap`` turns into the reference's
+    IndexError."""
+    from ..util.objects import describe_instances
+    assert len(coords) == len(masks) == len(instance_labels)
+    out, gt = [], []
+    for c, ms, lab in zip(coords, masks, instance_labels):
+        n = int(c.shape[0])
+        assert tuple(c.shape) == (n, 3) and tuple(lab.shape) == (n,), 'coords [n, 3] and labels [n] per scan'
+        table = describe_instances([dict(pred_mask=m) for m in ms], c, yaw_steps=yaw_steps, refine=refine,
+                                   backend=backend)
+        if (table['npoint'] == 0).any():
+            raise ValueError('zero-size array to reduction operation minimum which has no identity')
+        out.append(np.asarray(table['obb'], np.float64).reshape(-1, 7))
+        lab = host(lab).astype(np.int64)
+        k = max(int(lab.max()) + 1, 0) if lab.size else 0
+        owners = [dict(pred_mask=(lab == i)) for i in range(k)]
+        gtab = describe_instances(owners, c, yaw_steps=yaw_steps, refine=refine, backend=backend)
+        first = np.full(k, -1, np.int64)
+        valid = np.flatnonzero((lab >= 0) & (lab < k))
+        first[lab[valid][::-1]] = valid[::-1]              # (the lowest point index is written last)
+        gt.append((np.asarray(gtab['obb'], np.float64).reshape(-1, 7), gtab['npoint'].astype(np.int64), first))
+    return out, gt
+
+
 def evaluate_box_ap(pred_insts, coords, semantic_labels, instance_labels, class_labels,
-                    iou_thresholds=(0.25, 0.5), sem_shift=2, use_07_metric=False, logger=None, device=None):
+                    iou_thresholds=(0.25, 0.5), sem_shift=2, use_07_metric=False, logger=None, device=None,
+                    boxes='aabb', mode='3d', yaw_steps=90, refine=0, backend='auto'):
     """Box AP of instance predictions, as the reference's tools/eval_det.py scores them.
+    boxes='aabb' (the default): the reference's axis-aligned boxes and ``get_iou``.  boxes='obb':
+    yaw-oriented boxes (``oriented_instance_boxes`` with ``yaw_steps`` / ``refine``) and ``get_iou_obb``
+    (mode '3d') or ``get_iou_bev`` (mode 'bev'); ``backend`` 'numpy' / 'device' forces both the boxes
+    and the matching onto one side, 'auto' leaves the boxes to ``describe_instances`` and the matching
+    to ``device``.
     pred_insts: per scan a list of dict(label_id (1-based into class_labels), conf, pred_mask (RLE dict
     or dense array)); coords, semantic_labels, instance_labels: per scan [n, 3] / [n] / [n].
     GT instance i in range(max + 1) takes the class of its first point and counts when that class is
     >= sem_shift (name class_labels[cls - sem_shift]).
     -> {iou_threshold: dict(rec, prec, ap, mAP)} with eval_sphere's dicts."""
     masks = [[p['pred_mask'] for p in preds] for preds in pred_insts]
-    pboxes, gts = instance_boxes(coords, masks, instance_labels, device=device)
+    iou_func = get_iou
+    if boxes == 'aabb':
+        pboxes, gts = instance_boxes(coords, masks, instance_labels, device=device)
+    elif boxes == 'obb':
+        if mode not in ('3d', 'bev') or backend not in ('auto', 'numpy', 'device'):
+            raise ValueError(f"mode {mode!r}: '3d' or 'bev'; backend {backend!r}: 'auto', 'numpy' or 'device'")
+        iou_func = get_iou_obb if mode == '3d' else get_iou_bev
+        device = {'numpy': 'cpu', 'device': 'cuda' if device is None else device, 'auto': device}[backend]
+        pboxes, gts = oriented_instance_boxes(coords, masks, instance_labels, yaw_steps, refine, backend)
+    else:
+        raise ValueError(f"boxes {boxes!r}: 'aabb' or 'obb'")
     pred_all, gt_all = {}, {}
     for si, (preds, boxes, (gb, cnt, first)) in enumerate(zip(pred_insts, pboxes, gts)):
         pred_all[si] = [(class_labels[int(p['label_id']) - 1], boxes[k], float(p['conf']))
@@ -473,7 +602,7 @@ def evaluate_box_ap(pred_insts, coords, semantic_labels, instance_labels, class_
                 gt.append((class_labels[cls_id - sem_shift], gb[i]))
         gt_all[si] = gt
     ths = list(iou_thresholds)
-    res = _eval_multi(pred_all, gt_all, ths, use_07_metric, get_iou, device, 'zero') if ths else []
+    res = _eval_multi(pred_all, gt_all, ths, use_07_metric, iou_func, device, 'zero') if ths else []
     out = {}
     for t, (rec, prec, ap) in zip(ths, res):
         m = np.mean(list(ap.values()))

@@ -10,6 +10,8 @@ from .resample import (grid_downsample, mask_bits_gather, mask_runs_from_bits,  
                        nearest_index)
 from .geometry import (grow_segments, grow_segments_numpy, knn, knn_numpy, point_normals,  # noqa: F401
                        point_normals_numpy)
+from .boxes import (box_iou, box_iou_numpy, box_nms, box_nms_numpy, boxes8,  # noqa: F401
+                    obb_iou_pair)
 from .split import mask_components, mask_components_numpy  # noqa: F401
 from .superpoint import (SuperpointIndex, mask_snap, mask_snap_numpy, superpoint_index,  # noqa: F401
                          superpoint_index_numpy, superpoint_vote, superpoint_vote_numpy)

@@ -14,6 +14,7 @@ from .superpoint import load_scannet_segs, refine_result, snap_instances  # noqa
 from .geometry import make_superpoints  # noqa: F401
 from .objects import (ObjectTable, box_corners, describe_instances, describe_result,  # noqa: F401
                       load_objects, save_objects)  # noqa: F401
+from .boxes import nms_boxes, nms_objects, take_rows  # noqa: F401
 from .cloud_io import read_cloud, read_ply, read_table  # noqa: F401
 from .render import (fit_view, look_at, montage, read_png, render_cloud, render_result,  # noqa: F401
                      save_renders, turntable, write_png)  # noqa: F401

@@ -7,6 +7,10 @@ the masks under <results>/pred_instance/predicted_masks/ (one value per point, n
 and scores them with eval_sphere for every --iou threshold (one IoU pass for all of them).
 
     python tools/eval_det.py --data-path dataset/scannetv2/val --results-path results --iou 0.25 0.5
+
+With --boxes obb the masks and GT instances get yaw-oriented boxes (--yaw-steps directions) and are
+scored by the oriented IoU, --mode 3d (volumes) or bev (the rectangles in the xy plane); the default
+--boxes aabb is the reference's evaluation.
 """
 import argparse
 import glob
@@ -57,6 +61,10 @@ def main(argv=None):
     ap.add_argument('--iou', type=float, nargs='+', default=[0.25], help='IoU thresholds')
     ap.add_argument('--use-07-metric', action='store_true', help='VOC07 11-point AP')
     ap.add_argument('--device', default=None, help="'cuda', 'cpu' or unset (the GPU when there is one)")
+    ap.add_argument('--boxes', choices=['aabb', 'obb'], default='aabb',
+                    help="'aabb': the reference's axis-aligned boxes; 'obb': yaw-oriented boxes and their IoU")
+    ap.add_argument('--mode', choices=['3d', 'bev'], default='3d', help="with --boxes obb: volume or bird's-eye IoU")
+    ap.add_argument('--yaw-steps', type=int, default=90, help='with --boxes obb: directions of the yaw sweep')
     args = ap.parse_args(argv)
     paths = sorted(glob.glob(osp.join(args.results_path, 'pred_instance', '*.txt')))
     preds, coords, sems, insts = [], [], [], []
@@ -69,7 +77,8 @@ def main(argv=None):
         insts.append(i)
     print('Evaluating...')
     res = evaluate_box_ap(preds, coords, sems, insts, CLASS_LABELS, iou_thresholds=args.iou,
-                          use_07_metric=args.use_07_metric, device=args.device)
+                          use_07_metric=args.use_07_metric, device=args.device, boxes=args.boxes, mode=args.mode,
+                          yaw_steps=args.yaw_steps)
     for t in args.iou:
         print(f'IoU threshold: {t}')
         print('mAP:', res[t]['mAP'])
