@@ -878,45 +878,13 @@ __device__ __forceinline__ bool big_barrier(int32_t *bar, int &epoch, int32_t *f
   return *lds_flag != 0;
 }
 
-// The same rendezvous without the arrival counter (SG_BFS_BIG_FLAGS=1; off by default, measured no faster): every workgroup
-// stores the level's tag into ITS flag word once its claims have drained, and polls all G flags with one
-// coalesced load -- store -> visible -> poll is ONE trip through the fabric where atomic arrive -> return ->
-// poll is two.  Flags only grow (a workgroup that is already a level ahead still satisfies the wait).
-__device__ __forceinline__ bool big_flags_barrier(unsigned *flags, unsigned tag, int32_t *fail, int *lds_flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  const int G = gridDim.x;
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    if (lane == 0) __hip_atomic_store(flags + blockIdx.x, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int ok = 1;
-    for (int w0 = 0; w0 < G && ok; w0 += 64) {
-      const int w = w0 + lane;
-      unsigned spins = 0;
-      while (true) {
-        const bool ready = w >= G || __hip_atomic_load(flags + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= tag;
-        if (__all(ready)) break;
-        __builtin_amdgcn_s_sleep(1);
-        if ((++spins & 1023u) == 0u &&
-            (spins > (1u << 24) || __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = 0;
-          break;
-        }
-      }
-    }
-    if (lane == 0) *lds_flag = ok;
-  }
-  __syncthreads();
-  return *lds_flag != 0;
-}
-
 // sync words: [0] barrier counter, [1] fail, [2..3] staging pool heads (per parity),
 // [64 ..] records: rec[parity][workgroup] = two self-validating 64-bit words (tag << 32 | value):
-// region offset and region length
+// region offset and region length; then kBigWgsMax idle words (a retired rendezvous's flags) that stay in the
+// count: it sizes the memset, places the LOCAL form's words behind it and is the smallest n that takes this path
 constexpr int kBigRecAt = 64;
-constexpr int kBigFlagsAt = kBigRecAt + 8 * kBigWgsMax;      // claim-done flags, one word per workgroup
-constexpr int kBigSyncWords = kBigFlagsAt + kBigWgsMax;
+constexpr int kBigSyncWords = kBigRecAt + 8 * kBigWgsMax + kBigWgsMax;
+static_assert(kBigSyncWords == 2368, "a threshold of the giant-cluster path: do not move it");
 
 //
 // FAST (the default; SG_BFS_BIG_FAST=0 selects the round-4 form): a level is a chain of dependent memory
@@ -940,7 +908,7 @@ __global__ void __launch_bounds__(kEmitThreads) bfs_emit_big_kernel(
     const int32_t *__restrict__ idx, const int4 *__restrict__ node_rec, const int2 *__restrict__ erec,
     const int32_t *__restrict__ seeds, const int32_t *__restrict__ cluster_offsets, int n_cluster,
     int32_t *owner_g, int32_t *wcnt, int32_t *stage0, int32_t *stage1, u64 *srec0, u64 *srec1, int priv_base,
-    int32_t *cluster_idxs, int32_t *sync, bool flag_barrier, bool trace_on, const int32_t *gate) {
+    int32_t *cluster_idxs, int32_t *sync, bool trace_on, const int32_t *gate) {
   if (gate != nullptr && *gate == 0) return;      // (the LOCAL form completed: nothing to redo)
   __shared__ int lds_scan[kEmitWaves];
   __shared__ int lds_flag, lds_off;
@@ -1160,11 +1128,7 @@ __global__ void __launch_bounds__(kEmitThreads) bfs_emit_big_kernel(
         }
       }
       stamp(2);
-      if (flag_barrier) {
-        if (!big_flags_barrier(reinterpret_cast<unsigned *>(sync + kBigFlagsAt), tag, fail, &lds_flag)) return;
-      } else if (!big_barrier(bar, epoch, fail, &lds_flag)) {
-        return;
-      }
+      if (!big_barrier(bar, epoch, fail, &lds_flag)) return;
       stamp(3);
       if (E >= 0) {
         // ---- emit of a cached level
@@ -2004,17 +1968,13 @@ int sg_bfs_cluster_label(const int32_t *bq_idxs, const int32_t *start_len, int n
   const int lanes = lanes_auto(n_edges, n, kNarrowMean);
   hipMemsetAsync(w.counters, 0, 64 * 4, stream);
   bfs_init_kernel<<<grid, 256, 0, stream>>>(n, w.parent, w.size, w.owner);
-  static const bool one_pass = getenv("SG_BFS_ONE_PASS") != nullptr;      // developer A/B knob: round 4's single pass
-  if (!one_pass) {
-    static const bool sample_env = getenv("SG_BFS_SAMPLE") != nullptr;      // developer A/B knob: union-find sampling pass
-    if (sample_env || !(list_flags & SG_LISTS_SORTED))
-      launch_union<1>(lanes_union, stream, bq_idxs, start_len, n, list_flags & SG_LISTS_SORTED,
-                      list_flags & SG_LISTS_RADIUS, w.parent, w.asym_nodes, w.counters);
-    else
-      bfs_hook_min_kernel<<<grid, 256, 0, stream>>>(bq_idxs, start_len, n, list_flags & SG_LISTS_SORTED,
-                                                   list_flags & SG_LISTS_RADIUS, w.parent);
-    bfs_compress_kernel<<<grid, 256, 0, stream>>>(n, w.parent);
-  }
+  if (!(list_flags & SG_LISTS_SORTED))
+    launch_union<1>(lanes_union, stream, bq_idxs, start_len, n, list_flags & SG_LISTS_SORTED,
+                    list_flags & SG_LISTS_RADIUS, w.parent, w.asym_nodes, w.counters);
+  else
+    bfs_hook_min_kernel<<<grid, 256, 0, stream>>>(bq_idxs, start_len, n, list_flags & SG_LISTS_SORTED,
+                                                 list_flags & SG_LISTS_RADIUS, w.parent);
+  bfs_compress_kernel<<<grid, 256, 0, stream>>>(n, w.parent);
   launch_union<0>(lanes_union, stream, bq_idxs, start_len, n, list_flags & SG_LISTS_SORTED,
                   list_flags & SG_LISTS_RADIUS, w.parent, w.asym_nodes, w.counters);
   bfs_flatten_kernel<<<grid, 256, 0, stream>>>(n, w.parent, w.lab);
@@ -2106,9 +2066,8 @@ int sg_bfs_cluster_emit(const int32_t *bq_idxs, const int32_t *start_len, int n,
   const bool has_big = big_on && n < (1 << 21) && sum_npoint > kBigMin && (!noted || t_bfs_note.max_kept > kBigMin);
   t_bfs_note.ws = nullptr;
   // the giant clusters' replay (16 workgroups, milliseconds) next to the per-cluster kernel (one workgroup per
-  // cluster, the rest of the chip): fork a side stream here, join behind both (SG_BFS_BIG_SIDE=0: one after the other)
-  static const bool side_env = !(getenv("SG_BFS_BIG_SIDE") && atoi(getenv("SG_BFS_BIG_SIDE")) == 0);
-  BfsSide *side = has_big && side_env && !want_stats ? bfs_side(stream) : nullptr;
+  // cluster, the rest of the chip): fork a side stream here, join behind both
+  BfsSide *side = has_big && !want_stats ? bfs_side(stream) : nullptr;
   hipStream_t main_stream = stream;
   BfsDefer *defer = t_bfs_defer;      // (one call's worth)
   t_bfs_defer = nullptr;
@@ -2127,9 +2086,6 @@ int sg_bfs_cluster_emit(const int32_t *bq_idxs, const int32_t *start_len, int n,
     static const int big_wgs_env = getenv("SG_BFS_BIG_WGS") ? atoi(getenv("SG_BFS_BIG_WGS")) : 16;   // developer knob
     const int big_wgs = big_wgs_env < 8 ? 8 : big_wgs_env > kBigWgsMax ? kBigWgsMax : big_wgs_env;
     int32_t *sync = w.asym_nodes;               // free after labelling; >= 64 + 8 * kBigWgsMax ints
-    // (developer knob; measured: no gain -- kitti 9.47 against 9.42 ms, stpls3d_pp 11.4-11.8 against 11.3-11.5,
-    //  profiles/r06_bfs_big_flags_ab.txt -- the arrival atomic is not what a level waits for; off)
-    static const bool flags_on = getenv("SG_BFS_BIG_FLAGS") && atoi(getenv("SG_BFS_BIG_FLAGS")) != 0;
     if (static_cast<size_t>(n) >= static_cast<size_t>(kBigSyncWords)) {
       hipMemsetAsync(sync, 0, kBigSyncWords * 4, stream);
       if (const char *e = getenv("SG_BFS_FORCE_FALLBACK"))      // test hook: pretend the barrier gave up
@@ -2184,11 +2140,11 @@ int sg_bfs_cluster_emit(const int32_t *bq_idxs, const int32_t *start_len, int n,
       if (big_fast_on() && big_wgs <= kBigFastWgs && w.big_stage[0] != nullptr)
         bfs_emit_big_kernel<true><<<big_wgs, kEmitThreads, 0, stream>>>(
             bq_idxs, w.label, w.erec, w.seeds, cluster_offsets, n_cluster, w.owner, w.wcnt, w.big_stage[0],
-            w.big_stage[1], w.big_rec[0], w.big_rec[1], n, cluster_idxs, sync, flags_on, want_stats, gate);
+            w.big_stage[1], w.big_rec[0], w.big_rec[1], n, cluster_idxs, sync, want_stats, gate);
       else
         bfs_emit_big_kernel<false><<<big_wgs, kEmitThreads, 0, stream>>>(
             bq_idxs, w.label, w.erec, w.seeds, cluster_offsets, n_cluster, w.owner, w.wcnt, w.parent, w.lab,
-            nullptr, nullptr, 0, cluster_idxs, sync, false, false, gate);
+            nullptr, nullptr, 0, cluster_idxs, sync, false, gate);
       // sync[1] != 0: the replay gave up somewhere (see big_barrier) -- redo the giant clusters on
       // the per-cluster kernel (same output, slower); both launches are no-ops otherwise
       bfs_owner_reset_kernel<<<grid_for(n, 256, 1024), 256, 0, stream>>>(n, w.label, w.size, kBigMin,

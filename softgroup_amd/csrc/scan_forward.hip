@@ -188,34 +188,18 @@ __global__ void __launch_bounds__(256) pack_segments_kernel(PackList p, char *__
   }
 }
 
-// ---- device -> pinned host copy of the dense results as a SMALL kernel (SG_SCAN_D2H_WGS workgroups; 0 = hipMemcpyAsync).
-// The runtime's copy of 12 MB is a shader blit with one workgroup on every CU (__amd_rocclr_copyBuffer, 219 us =
-// the PCIe rate); whatever runs next to it is stretched to its end (bfs_seed_kernel 5 -> 130 us, select_scan_kernel
-// 20 -> 229 us in round 5's traces): its stalled system-memory stores sit in every CU's memory queue.  A few workgroups
-// move the same bytes at the same PCIe rate and leave the other CUs' queues alone.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__global__ void __launch_bounds__(256) d2h_copy_kernel(const u32x4 *__restrict__ src, u32x4 *__restrict__ dst, size_t n16) {
-  for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n16; i += gridDim.x * 256ull)
-    __builtin_nontemporal_store(src[i], dst + i);
-}
-
 // ---- per (device, caller stream): the side stream of the dense results' copy and its two events
 struct ScanStream {
   hipStream_t copy = nullptr;
   hipEvent_t packed = nullptr, copied = nullptr, backbone_done = nullptr;
 };
-// Backbone token: with several scans in flight on one
-// device (one host thread and stream each) only ONE of them is inside its backbone -- the part of a scan
-// whose kernels fill the whole chip and gain nothing from running next to another backbone -- while the
-// others' grouping / refinement stages (small grids, host read-backs) run in its shadow.  Scans that
-// start together no longer move through their phases in lock step.
-// Form 2 (SG_SCAN_TOKEN=2) orders the backbones on the GPU instead of on the host: the convolutions of a scan
-// wait (hipStreamWaitEvent) for the event behind the previous scan's backbone, whichever stream that ran on; the
-// mutex is held only while the backbone is being enqueued, nobody blocks on the device.
-static std::mutex g_backbone_mu[16];
-static hipEvent_t g_backbone_last[16];        // event behind the latest backbone enqueued on the device (under the mutex)
-// Form 4 (SG_SCAN_TOKEN=4): like form 1 with SG_SCAN_TOKEN_PERMITS (default 2) backbones at a time -- a counting
-// semaphore instead of the mutex.
+// Backbone token: with several scans in flight on one device (one host thread and stream each) at most
+// SG_SCAN_TOKEN_PERMITS (default 2) of them are inside their backbone -- the part of a scan whose kernels fill the
+// whole chip and gain nothing from running next to more backbones -- while the others' grouping / refinement stages
+// (small grids, host read-backs) run in their shadow.  Scans that start together no longer move through their phases
+// in lock step.  A counting semaphore held by the host: a permit is taken in sg_unet_forward's pre-conv hook and given
+// back when the event behind the backbone has completed.  (The forms that lost -- one permit, the order kept on the
+// GPU by an event wait, the token held from before the index build -- are in profiles/r06_token_matrix.txt.)
 struct BackboneSem {
   std::mutex m;
   std::condition_variable cv;
@@ -228,37 +212,24 @@ static int backbone_permits() {
 }
 struct BackboneToken {
   int dev;
-  hipStream_t stream;
-  std::unique_lock<std::mutex> lock;
   bool taken = false;
-  bool sem = false;      // form 4: a permit of g_backbone_sem instead of the mutex
 };
 static void backbone_token_take(void *ctx) {      // (sg_unet_forward's pre-conv hook)
   BackboneToken *t = static_cast<BackboneToken *>(ctx);
-  if (t->sem) {
-    BackboneSem &s = g_backbone_sem[t->dev];
-    std::unique_lock<std::mutex> g(s.m);
-    s.cv.wait(g, [&] { return s.in_use < backbone_permits(); });
-    ++s.in_use;
-    t->taken = true;
-    return;
-  }
-  t->lock = std::unique_lock<std::mutex>(g_backbone_mu[t->dev]);
+  BackboneSem &s = g_backbone_sem[t->dev];
+  std::unique_lock<std::mutex> g(s.m);
+  s.cv.wait(g, [&] { return s.in_use < backbone_permits(); });
+  ++s.in_use;
   t->taken = true;
-  if (g_backbone_last[t->dev] != nullptr) hipStreamWaitEvent(t->stream, g_backbone_last[t->dev], 0);
 }
 static void backbone_token_give(BackboneToken *t) {
   if (!t->taken) return;
-  if (t->sem) {
-    BackboneSem &s = g_backbone_sem[t->dev];
-    {
-      std::lock_guard<std::mutex> g(s.m);
-      --s.in_use;
-    }
-    s.cv.notify_one();
-  } else {
-    t->lock.unlock();
+  BackboneSem &s = g_backbone_sem[t->dev];
+  {
+    std::lock_guard<std::mutex> g(s.m);
+    --s.in_use;
   }
+  s.cv.notify_one();
   t->taken = false;
 }
 static std::mutex g_scan_mu;
@@ -290,10 +261,6 @@ void scan_release_stream(int dev, hipStream_t stream) {
     hipStreamDestroy(it->second.copy);
     hipEventDestroy(it->second.packed);
     hipEventDestroy(it->second.copied);
-    if (dev >= 0 && dev < 16) {
-      std::lock_guard<std::mutex> b(g_backbone_mu[dev]);
-      if (g_backbone_last[dev] == it->second.backbone_done) g_backbone_last[dev] = nullptr;
-    }
     hipEventDestroy(it->second.backbone_done);
   }
   g_scan_streams.erase(it);
@@ -312,23 +279,14 @@ static void start_dense_copy(void *ctx) {
   if (d->issued || d->bytes == 0) return;
   d->issued = true;
   // the copy waits for the point where the caller's stream is NOW (the packed block is long complete)
-  static const int d2h_wgs = getenv("SG_SCAN_D2H_WGS") ? atoi(getenv("SG_SCAN_D2H_WGS")) : 0;
-  // (SG_SCAN_COPY_STREAM=0, developer A/B: the copy on the caller's stream, in line, instead of the side stream)
-  static const bool side = !(getenv("SG_SCAN_COPY_STREAM") && atoi(getenv("SG_SCAN_COPY_STREAM")) == 0);
-  hipStream_t cs = side ? d->ss->copy : d->main;
-  if (side && (hipEventRecord(d->ss->packed, d->main) != hipSuccess ||
-               hipStreamWaitEvent(d->ss->copy, d->ss->packed, 0) != hipSuccess)) {
+  if (hipEventRecord(d->ss->packed, d->main) != hipSuccess ||
+      hipStreamWaitEvent(d->ss->copy, d->ss->packed, 0) != hipSuccess) {
     d->failed = true;
     return;
   }
-  if (d2h_wgs > 0 && d->bytes % 16 == 0) {
-    d2h_copy_kernel<<<d2h_wgs, 256, 0, cs>>>(static_cast<const u32x4 *>(d->dev_block),
-                                             static_cast<u32x4 *>(d->host_block), d->bytes / 16);
-    if (hipGetLastError() != hipSuccess) d->failed = true;
-  } else if (hipMemcpyAsync(d->host_block, d->dev_block, d->bytes, hipMemcpyDeviceToHost, cs) != hipSuccess) {
+  if (hipMemcpyAsync(d->host_block, d->dev_block, d->bytes, hipMemcpyDeviceToHost, d->ss->copy) != hipSuccess)
     d->failed = true;
-  }
-  if (hipEventRecord(d->ss->copied, cs) != hipSuccess) d->failed = true;
+  if (hipEventRecord(d->ss->copied, d->ss->copy) != hipSuccess) d->failed = true;
 }
 
 static Mlp2 as_mlp(const sg_mlp2 &m) { return Mlp2{m.w1, m.b1, m.bn_scale, m.bn_shift, m.w2, m.b2, m.out}; }
@@ -501,32 +459,29 @@ int sg_scan_forward(const sg_scan_desc *d, const sg_scan_input *in, void *arena,
   res->semantic_preds = ar.at(preds);
 
   // ---- 1. voxel feature pooling, backbone, point-wise heads, softmax
-  // (default: form 4, two backbones at a time -- 2.66-2.83 ms/scan, median 2.70, against 2.74-3.04, median 2.81,
+  // (backbone token, two backbones at a time -- 2.66-2.83 ms/scan, median 2.70, against 2.74-3.04, median 2.81,
   //  without a token over six interleaved runs of the bench's default region; 3.28-3.54 against 3.33-3.49 at 20 steps;
-  //  three permits: no gain; one permit, form 1: 2.70-2.85 but outliers of 4.1 / 4.6 at 20 steps.
+  //  three permits: no gain; one permit: 2.70-2.85 but outliers of 4.1 / 4.6 at 20 steps.
   //  profiles/r06_token_matrix.txt.  SG_SCAN_TOKEN=0: off)
-  static const int token_env = getenv("SG_SCAN_TOKEN") ? atoi(getenv("SG_SCAN_TOKEN")) : 4;
-  int token_mode = 0;
+  static const bool token_env = !(getenv("SG_SCAN_TOKEN") && atoi(getenv("SG_SCAN_TOKEN")) == 0);
+  bool token_on = false;
   int dev = 0;
-  if (token_env != 0 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
+  if (token_env && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
     std::lock_guard<std::mutex> g(g_scan_mu);
     int n = 0;
     for (const auto &kv : g_scan_streams) n += kv.first.first == dev;
-    if (n > 1) token_mode = token_env;      // (a single caller stream: nothing to order)
+    token_on = n > 1;      // (a single caller stream: nothing to order)
   }
-  const bool use_token = token_mode == 3;       // (3: host-held from before the index build, the first form measured)
-  std::unique_lock<std::mutex> token;
-  if (use_token) token = std::unique_lock<std::mutex>(g_backbone_mu[dev]);
-  BackboneToken bt{dev, stream, {}, false, token_mode == 4};
+  BackboneToken bt{dev};
   struct TokenHookScope {      // (the hook is cleared by sg_unet_forward when it runs; here for the error paths before that)
     BackboneToken &t;
     ~TokenHookScope() {
       t_unet_conv_hook = nullptr;
       t_unet_conv_ctx = nullptr;
-      if (t.sem) backbone_token_give(&t);      // (an error return between the hook and the hand-back below)
+      backbone_token_give(&t);      // (an error return between the hook and the hand-back below)
     }
   } token_hook_scope{bt};
-  if (token_mode == 1 || token_mode == 2 || token_mode == 4) {
+  if (token_on) {
     t_unet_conv_hook = backbone_token_take;
     t_unet_conv_ctx = &bt;
   }
@@ -556,10 +511,8 @@ int sg_scan_forward(const sg_scan_desc *d, const sg_scan_input *in, void *arena,
   }
   SG_TRY_(check_launch(kWhat));
   if (bt.taken) {       // behind this point of the stream the next scan's convolutions may run
-    if (hipEventRecord(ss->backbone_done, stream) == hipSuccess) {
-      if (!bt.sem) g_backbone_last[dev] = ss->backbone_done;
-      if (token_mode == 1 || token_mode == 4) hipEventSynchronize(ss->backbone_done);      // forms 1, 4: the host holds the token until then
-    }
+    if (hipEventRecord(ss->backbone_done, stream) == hipSuccess)
+      hipEventSynchronize(ss->backbone_done);      // the host holds the permit until then
     backbone_token_give(&bt);
   }
   DenseCopy dc{ss, stream, dense_dev, host_dense, dense_total, false, false};
@@ -585,13 +538,6 @@ int sg_scan_forward(const sg_scan_desc *d, const sg_scan_input *in, void *arena,
     return SG_OK;
   }
   SG_TRY_(sg_softmax_rows(sem, N, ns, prob, stream_));
-  if (use_token) {      // the next scan's backbone may start when this one's has left the GPU
-    if (hipEventRecord(ss->backbone_done, stream) != hipSuccess || hipEventSynchronize(ss->backbone_done) != hipSuccess) {
-      set_error("%s: waiting for the backbone failed", kWhat);
-      return SG_ERR_LAUNCH;
-    }
-    token.unlock();
-  }
 
   // ---- 2. grouping head + proposal voxelisation (its sub-arena starts at the scratch mark)
   sg_grouping_cfg gc = d->grouping;

@@ -1591,10 +1591,9 @@ static int chain_flush() {
   }
   const size_t lds = static_cast<size_t>(kChainWV) * 16 * 64 * sizeof(float) + 2 * kMetaInts * sizeof(int32_t) + 16 +
                      static_cast<size_t>(kChainWV) * 4096;
-  // (developer knobs: SG_CHAIN_GRID = workgroups of a chain launch, at most one per CU; SG_CHAIN_SERIAL=0 lets chain
-  // launches of different streams overlap -- only safe while all of them together fit the device)
+  // (developer knob: SG_CHAIN_GRID = workgroups of a chain launch, at most one per CU.  Chain launches of different
+  // streams never overlap: the barriers of partially resident chains would time out)
   static const int grid_env = getenv("SG_CHAIN_GRID") ? atoi(getenv("SG_CHAIN_GRID")) : 0;
-  static const bool serial = !(getenv("SG_CHAIN_SERIAL") && atoi(getenv("SG_CHAIN_SERIAL")) == 0);
   int grid = num_cu >= 8 ? num_cu - num_cu % 8 : num_cu;
   if (grid_env >= 8 && grid_env < grid) grid = grid_env - grid_env % 8;
   const bool prof = g_conv_prof.enabled && c.conv_steps > 0;
@@ -1617,7 +1616,7 @@ static int chain_flush() {
       return SG_ERR_LAUNCH;
     }
     hipEvent_t &last = g_chain_last[dev];
-    if (serial && last != nullptr && last != mine) hipStreamWaitEvent(c.stream, last, 0);    // one chain at a time per device
+    if (last != nullptr && last != mine) hipStreamWaitEvent(c.stream, last, 0);    // one chain at a time per device
     if (prof) {
       hipEventRecord(g_conv_prof.take(), c.stream);
       for (int v : {-c.conv_steps, 0, 0, 0, 0}) g_conv_prof.dims.push_back(v);
@@ -1833,8 +1832,8 @@ static void decide_persistent_split(ConvLaunch &d, int K, int Cin, int Cout, boo
   // fill the two-wave slots 1.5 times over keep four or eight waves (128->128 x 4.7 k rows: 35 -> 60 us
   // if forced).  SG_CONV_W2_MAX = largest K * Cin / 32 (items of a full tile) they are used for.
   static const int w2_max = getenv("SG_CONV_W2_MAX") ? atoi(getenv("SG_CONV_W2_MAX")) : 108;
-  static const int w2_nbw = getenv("SG_CONV_W2_NBW") ? atoi(getenv("SG_CONV_W2_NBW")) : 2;      // A/B knob
-  static const float w2_rounds = getenv("SG_CONV_W2_ROUNDS") ? atof(getenv("SG_CONV_W2_ROUNDS")) : 1.5f;
+  constexpr int kW2Nbw = 2;             // widest column unit (32-column blocks) of a two-wave variant
+  constexpr float kW2Rounds = 1.5f;     // how many times over the units must fill the two-wave slots
   const bool use_w2 = wv_env == 2 || (wv_env == 0 && K * (Cin / 32) <= w2_max);
   // (One wave per unit was measured too: the heaviest tiles -- 27 offsets in a single wave -- then
   // set the span of the big layers, 32->32 x 124 k rows 28.5 -> 32.1 us, 64->64 x 77 k 52 -> 69 us; on
@@ -1842,7 +1841,7 @@ static void decide_persistent_split(ConvLaunch &d, int K, int Cin, int Cout, boo
   for (int i = 0; i < kSplitVariants; ++i) {
     const SplitVariant &v = g_split_variants[i];
     if (v.at != use_at) continue;
-    if (v.wv == 2 && (!use_w2 || ksplit > 1 || v.nbw > w2_nbw)) continue;
+    if (v.wv == 2 && (!use_w2 || ksplit > 1 || v.nbw > kW2Nbw)) continue;
     if (ksplit > 1) {
       // (8 waves per unit on these layers: 2.482 against 2.492 ms per backbone forward, no difference)
       if (v.nbw == 1 && v.wv == 4) { pick = i; break; }
@@ -1852,7 +1851,7 @@ static void decide_persistent_split(ConvLaunch &d, int K, int Cin, int Cout, boo
     if (v.nbw == 2 && (Cout % 64 != 0 || nbw_env < 2)) continue;
     if (wv_env && v.wv != wv_env) continue;
     const long long units = static_cast<long long>(num_tiles) * (NB / v.nbw);
-    if (wv_env || units >= static_cast<long long>((v.wv == 2 ? w2_rounds : min_rounds) * num_cu * (in16 ? v.occ_r16 : b16 ? v.occ_b16 : v.occ))) {
+    if (wv_env || units >= static_cast<long long>((v.wv == 2 ? kW2Rounds : min_rounds) * num_cu * (in16 ? v.occ_r16 : b16 ? v.occ_b16 : v.occ))) {
       pick = i;
       break;
     }
@@ -1921,10 +1920,10 @@ static ConvLaunch conv_launch_decide(int M_out, int num_in_rows, int K, int Cin,
                           static_cast<long long>(M_out) * Cout * 4 * kMaxK < (1LL << 32) &&
                           static_cast<long long>(num_tiles) * kTileRows * K * 4 < (1LL << 31) && have_plan;
   // split-precision path (fp32 products as six bf16 MFMAs, see split3): the default for every layer
-  // the persistent kernel takes with Cin >= SG_CONV_SPLIT_MIN_CIN (SG_CONV_SPLIT=0: the fp32-MFMA
+  // the persistent kernel takes with Cin >= kSplitMinCin (SG_CONV_SPLIT=0: the fp32-MFMA
   // kernel, kept for A/B)
-  static const int split_min_cin = getenv("SG_CONV_SPLIT_MIN_CIN") ? atoi(getenv("SG_CONV_SPLIT_MIN_CIN")) : 16;
-  const bool split = persistent && split_on != 0 && Cin >= split_min_cin;
+  constexpr int kSplitMinCin = 16;
+  const bool split = persistent && split_on != 0 && Cin >= kSplitMinCin;
   d.persistent = persistent;
   d.split = split;
   // ---- decomposition: aim at >= ~2048 waves; the general kernel widens its column block while
@@ -1966,7 +1965,7 @@ static ConvLaunch conv_launch_decide(int M_out, int num_in_rows, int K, int Cin,
     decide_persistent_split(d, K, Cin, Cout, split_on == 2, in16, chain_open);
   } else if (persistent) {
     // fp32-MFMA kernel (SG_CONV_SPLIT=0 / sg_spconv_set_arithmetic(0), and layers below
-    // SG_CONV_SPLIT_MIN_CIN): 16-channel slices, 2-deep operand ring, 4 waves per unit, one column
+    // kSplitMinCin): 16-channel slices, 2-deep operand ring, 4 waves per unit, one column
     // block; as many workgroups as are resident at once (a multiple of 8 so that unit u always runs
     // on XCD u % 8).  (Rounds 1-3 also carried 4- and 8-deep rings, an 80-VGPR build and 64-column
     // units of this kernel; none of them was faster and they are gone.)

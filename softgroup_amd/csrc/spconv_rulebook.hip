@@ -703,8 +703,6 @@ static int build_plans(const PlanSegs &P, void *ws2, size_t ws2_bytes, bool zero
   }
   const dim3 grid((max_rows + 255) / 256, P.n);
   plan_mask_all_kernel<<<grid, 256, 0, stream>>>(P, mask, val, freq);
-  static const bool raw_env = getenv("SG_PLAN_RAW") != nullptr;     // developer knob: sort by the raw mask
-  if (raw_env) hipMemsetAsync(freq, 0, kPyrMaxSegs * 32 * 4, stream);   // equal counts -> identity permutation
   plan_pos_all_kernel<<<P.n, 32, 0, stream>>>(P, freq, bitpos);
   const int mode = plan_order_mode();
   // ---- big tables: one device-wide radix sort, the table's index in the key bits above the mask

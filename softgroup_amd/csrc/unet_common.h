@@ -48,8 +48,8 @@ struct LevelIdx {
   } while (0)
 
 // Tables and plans of all `n_levels` levels of the voxel pyramid over `indices`, laid out from the
-// start of `arena` (-> *used bytes), built on an internal index stream that the caller's stream then
-// waits for; one host synchronisation (the level row counts).  Per-(device, stream) runtime state;
+// start of `arena` (-> *used bytes), built on the caller's stream;
+// one host synchronisation (the level row counts).  Per-(device, stream) runtime state;
 // `*lock` holds that state's mutex until the caller lets go of it (calls on one stream are serial).
 int unet_build_index(const char *who, int n_levels, const int32_t *indices, int num_rows,
                      const int32_t *spatial_shape_host, void *arena, size_t arena_bytes, sg_stream_t stream,

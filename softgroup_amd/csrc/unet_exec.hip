@@ -9,9 +9,9 @@
 // discipline per level) and ONE host sync per forward.  Everything that depends only on voxel
 // coordinates -- the gather tables and tile plans of ALL levels -- is built up front by the
 // whole-pyramid index build (sg_spconv_pyramid_rows / _build, spconv_rulebook.hip): ~30 launches
-// and one read-back of the level row counts for the entire U-Net, on an internal index stream;
-// the caller's stream waits for it once and then runs nothing but convolutions.
-// Runtime state (index stream, events, pinned read-back words) is kept per (device, caller
+// and one read-back of the level row counts for the entire U-Net, on the caller's stream,
+// which then runs nothing but convolutions.
+// Runtime state (the pinned and device read-back words) is kept per (device, caller
 // stream): concurrent scans on different streams do not share any of it.
 #include <map>
 #include <mutex>
@@ -166,18 +166,12 @@ __global__ void __launch_bounds__(256) ident_plan_kernel(IdentSegs s) {
 }
 
 // ---- runtime state per (device, caller's stream): callers that run scans concurrently on
-//      several streams (one host thread each) get an index stream of their own and never wait for
+//      several streams (one host thread each) get row-count buffers of their own and never wait for
 //      each other; calls on the same stream are serialised by the state's mutex
-static bool index_stream_on() {      // SG_UNET_INDEX_STREAM=1: the index build on a stream of its own (see unet_build_index)
-  static const bool on = getenv("SG_UNET_INDEX_STREAM") && atoi(getenv("SG_UNET_INDEX_STREAM")) != 0;
-  return on;
-}
 struct StreamState {
   std::mutex mu;
   int32_t *host_rows = nullptr;     // pinned [SG_PYRAMID_MAX_LEVELS]
   int32_t *dev_rows = nullptr;      // device
-  hipStream_t istream = nullptr;
-  hipEvent_t ev_start = nullptr, ev_index = nullptr;
   bool ready = false;
 };
 static std::mutex table_mu;
@@ -196,12 +190,6 @@ void unet_release_stream(int dev, hipStream_t stream) {
   {
     std::lock_guard<std::mutex> g(st->mu);      // (no forward of that stream is inside the build)
     if (st->ready) {
-      if (st->istream != nullptr) {
-        hipStreamSynchronize(st->istream);
-        hipStreamDestroy(st->istream);
-      }
-      hipEventDestroy(st->ev_start);
-      hipEventDestroy(st->ev_index);
       hipHostFree(st->host_rows);
       hipFree(st->dev_rows);
     }
@@ -228,28 +216,12 @@ int unet_build_index(const char *who, int L, const int32_t *indices, int num_row
                "%s: pinned allocation failed", who);
     SG_REQUIRE(hipMalloc(reinterpret_cast<void **>(&st.dev_rows), SG_PYRAMID_MAX_LEVELS * 4) == hipSuccess,
                "%s: device allocation failed", who);
-    SG_REQUIRE(!index_stream_on() || hipStreamCreateWithFlags(&st.istream, hipStreamNonBlocking) == hipSuccess,
-               "%s: stream creation failed", who);
-    SG_REQUIRE(hipEventCreateWithFlags(&st.ev_start, hipEventDisableTiming) == hipSuccess &&
-                   hipEventCreateWithFlags(&st.ev_index, hipEventDisableTiming) == hipSuccess,
-               "%s: event creation failed", who);
     st.ready = true;
   }
-  // The index build runs on the CALLER's stream (since the end of round 6).  Until then it had a stream of its own per
-  // caller stream, so that the host's wait for the row counts did not wait for whatever the caller had queued; with the
-  // scan as one C call nothing is queued there, and one stream less per scan worker measured 2.42-2.57 against 2.66-2.81
-  // ms/scan with five scans in flight (five interleaved pairs), 3.20-3.48 against 3.38-3.91 in the 20-step region and
-  // 4.49 / 4.57 against 4.61 / 4.61 ms for one scan (profiles/r06_index_stream.txt).  SG_UNET_INDEX_STREAM=1: as before.
-  const bool own_istream = index_stream_on();
-  hipStream_t istream = own_istream ? st.istream : as_stream(stream);
-  sg_stream_t is = reinterpret_cast<sg_stream_t>(istream);
-  // the index stream starts where the caller's stream is now: the coordinates are ready, and the
-  // previous forward's convolutions no longer read the tables about to be overwritten
-  if (own_istream && (hipEventRecord(st.ev_start, as_stream(stream)) != hipSuccess ||
-                      hipStreamWaitEvent(istream, st.ev_start, 0) != hipSuccess)) {
-    set_error("%s: event record/wait failed", who);
-    return SG_ERR_LAUNCH;
-  }
+  // The index build runs on the CALLER's stream.  A stream of its own per caller stream (so that the host's wait for
+  // the row counts did not wait for whatever the caller had queued) lost once the scan was one C call with nothing
+  // queued there: 2.66-2.81 against 2.42-2.57 ms/scan with five scans in flight (profiles/r06_index_stream.txt).
+  hipStream_t hs = as_stream(stream);
   // ---- index part of the arena (bump, never recycled inside a forward)
   Arena ix(arena, arena_bytes);
 #define SG_IALLOC(var, T, count)                                                       \
@@ -258,13 +230,12 @@ int unet_build_index(const char *who, int L, const int32_t *indices, int num_row
     set_error("%s: arena too small (%zu bytes) for the index tables", who, arena_bytes); \
     return SG_ERR_WORKSPACE;                                                           \
   }
-  // ---- rows of every level: one pass + one read-back (the only host sync of the forward; it
-  //      waits for the index stream only -- whatever the caller's stream has queued keeps running)
+  // ---- rows of every level: one pass + one read-back (the only host sync of the forward)
   const size_t pws_bytes = sg_spconv_pyramid_workspace_bytes(num_rows, L);
   SG_IALLOC(pws, char, pws_bytes);
-  SG_TRY(sg_spconv_pyramid_rows(indices, num_rows, spatial_shape_host, L, st.dev_rows, pws, pws_bytes, is));
-  if (hipMemcpyAsync(st.host_rows, st.dev_rows, sizeof(int32_t) * L, hipMemcpyDeviceToHost, istream) != hipSuccess ||
-      hipStreamSynchronize(istream) != hipSuccess) {
+  SG_TRY(sg_spconv_pyramid_rows(indices, num_rows, spatial_shape_host, L, st.dev_rows, pws, pws_bytes, stream));
+  if (hipMemcpyAsync(st.host_rows, st.dev_rows, sizeof(int32_t) * L, hipMemcpyDeviceToHost, hs) != hipSuccess ||
+      hipStreamSynchronize(hs) != hipSuccess) {
     set_error("%s: reading the level row counts failed", who);
     return SG_ERR_LAUNCH;
   }
@@ -314,7 +285,7 @@ int unet_build_index(const char *who, int L, const int32_t *indices, int num_row
   {
     const size_t nb = sg_spconv_pyramid_build_workspace_bytes(pl, L);
     SG_IALLOC(ws2, char, nb);
-    SG_TRY(sg_spconv_pyramid_build(indices, num_rows, spatial_shape_host, L, pl, pws, pws_bytes, ws2, nb, is));
+    SG_TRY(sg_spconv_pyramid_build(indices, num_rows, spatial_shape_host, L, pl, pws, pws_bytes, ws2, nb, stream));
   }
   if (L > 1) {      // trivial plans of the 1x1 convs on the tail's identity branches
     IdentSegs segs;
@@ -330,14 +301,9 @@ int unet_build_index(const char *who, int L, const int32_t *indices, int num_row
       P.nbr = ord; P.order = ord; P.nbr_tiles = ord; P.tile_mask = tm;
       P.rows = li[l].rows; P.kvol = 1;
     }
-    ident_plan_kernel<<<dim3(grid_for(num_rows, 256), L - 1), 256, 0, istream>>>(segs);
+    ident_plan_kernel<<<dim3(grid_for(num_rows, 256), L - 1), 256, 0, hs>>>(segs);
   }
 #undef SG_IALLOC
-  if (own_istream && (hipEventRecord(st.ev_index, istream) != hipSuccess ||
-                      hipStreamWaitEvent(as_stream(stream), st.ev_index, 0) != hipSuccess)) {
-    set_error("%s: event record/wait failed", who);
-    return SG_ERR_LAUNCH;
-  }
   *used = ix.off;
   *lock = std::move(guard);
   return SG_OK;
@@ -547,7 +513,7 @@ struct Exec {
         SG_TRY(chain.close());
       }
       // ---- SparseInverseConv3d(c2, c): gather table = parent row per fine voxel (plan `up`, built
-      //      on the index stream before the descent), then the skip concat (blocks.py:135-139)
+      //      by the index build before the descent), then the skip concat (blocks.py:135-139)
       //      with the first tail block's BatchNorm + ReLU as a second output
       SG_ALLOC(cat, float, 2 * feat);
       SG_ALLOC(cata, float, 2 * feat);
@@ -711,7 +677,7 @@ int sg_unet_forward(const sg_unet_desc *d, const float *feats, const int32_t *in
   const size_t head_bytes = align_up(head.off, 4096);
   char *rest = static_cast<char *>(arena) + head_bytes;
   const size_t rest_bytes = arena_bytes > head_bytes ? arena_bytes - head_bytes : 0;
-  // ---- gather tables and tile plans of all levels (index stream; this stream waits for them once)
+  // ---- gather tables and tile plans of all levels (on this stream; one host sync)
   LevelIdx li[SG_PYRAMID_MAX_LEVELS];
   std::unique_lock<std::mutex> guard;
   size_t index_bytes = 0;

@@ -1,5 +1,5 @@
 """Full-model forward_train + backward + Adam, fp32, 8 steps: what `rocprofv3 --kernel-trace --stats` is pointed at
-(tools/r06/r06_gpu_train_prof.sh).  Usage (GPU box): python tools/train_step_profile.py [points] [fp32|bf16]"""
+(profiles/r06_train_profile.txt).  Usage (GPU box): python tools/train_step_profile.py [points] [fp32|bf16]"""
 import copy
 import os
 import sys
